@@ -17,7 +17,9 @@ at N=8, the same per-GPU work at N=1/2/4 (weak scaling).  ``--size 512 --batch-p
 config[1].  Everything inside the timed region is real: G and D forward/backward through the HIP
 kernels, R1 / path-length double-backward, Adam steps, EMA, gradient all-reduce.
 
-Rank 0 prints ONE JSON line with the contract fields plus
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times --steps iterations and prints the contract fields (metric, value,
+unit, higher_is_better, dtype, ms_per_step, ...), the losses of the last step and phases_fired; --dump-outputs DIR also writes what the
+last timed step left to its caller (see dump_outputs).  Everything else needs --full, which adds
   "roofline":      the dominant kernel's achieved TFLOP/s (algorithmic flops / HIP-event time on the
                    launch stream, measured inside the timed region) against the fp32 MFMA peak,
   "cpu_baseline":  the oracle (CPU restatement of the reference FUSED=False path) timed on the
@@ -27,8 +29,11 @@ Rank 0 prints ONE JSON line with the contract fields plus
                    achieved rate against its roofline -- from one UNTIMED pass of 16 iterations under torch.profiler
                    after the timed region,
   "step_roofline": algorithmic convolution TFLOP per step (tallied launch by launch over that pass) / ms_per_step,
-  "phases_fired":  how many lazy-regulariser passes fell inside the timed window,
+  "kernels":       HIP-event time and rate of the launches bracketed in the timed region,
+  "fp32_exact":    the same workload timed once more in exact fp32 arithmetic,
+  "host_issue":    host wall time of one cadence cycle issued into a drained device,
   "comm":          (N > 1) gradient bytes handed to RCCL per step and the compute-stream stall they caused.
+The --no-* switches below turn single parts of --full off again.
 """
 import argparse
 import json
@@ -61,6 +66,11 @@ def parse(argv=None):
     ap.add_argument('--batch-per-gpu', type=int, default=4)
     ap.add_argument('--precision', default=os.environ.get('GANCONTROL_CONV_PRECISION', 'bf16x3'), choices=['f32', 'bf16x3', 'bf16'],
                     help='conv arithmetic: bf16x3 = split-bf16 MFMA (fp32 storage, ~5e-6 relative error per layer), f32 = exact fp32 MFMA')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline figure: kernel timers and rooflines, the exact-fp32 leg, the per-family profiler pass, '
+                         'host issue time, gradient communication (N > 1) and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last one left to its caller as DIR/<name>.npy (see dump_outputs)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-fp32-leg', action='store_true', help='skip the second timed region in exact fp32 arithmetic ("fp32_exact" in the JSON line)')
     ap.add_argument('--no-kernel-timer', action='store_true')
@@ -400,6 +410,26 @@ def cpu_baseline(size):
     return out
 
 
+DUMP_SAMPLE = 1 << 22        # values kept per network (16 MiB of float32): three networks stay below 64 MB in all
+
+
+def dump_outputs(trainer, stats, out_dir):
+    """What the last timed step hands its caller, as ``out_dir/<name>.npy``: the updated parameters of ``generator``, ``discriminator`` and
+    ``g_ema`` (float32, each network's parameters flattened in named_parameters() order; a network with more than DUMP_SAMPLE values keeps
+    the same seeded sample of DUMP_SAMPLE positions in every run) and the scalar statistics of the line's "losses" as ``loss_<name>``
+    (float64).  The inputs are seeded (GeneratorTrainer seed 0), so two builds run with the same arguments can be compared file by file."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, net in (('generator', trainer.generator), ('discriminator', trainer.discriminator), ('g_ema', trainer.g_ema)):
+        flat = torch.cat([p.detach().reshape(-1) for _, p in net.named_parameters()])
+        if flat.numel() > DUMP_SAMPLE:
+            idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+            flat = flat[idx.to(flat.device)]
+        np.save(os.path.join(out_dir, name + '.npy'), flat.float().cpu().numpy())
+    for k, v in stats.items():
+        np.save(os.path.join(out_dir, 'loss_%s.npy' % k), np.array([v], dtype=np.float64))
+
+
 # Tests only (tests/bench_emulated_entry.py): the launcher / rank plumbing of this file exercised on CPUs over gloo with the emulated
 # C ABI installed by the test entry.  Never set by bench.py itself: without it the bench refuses to run without a GPU.
 _TEST_CPU = {'enabled': False}
@@ -453,6 +483,8 @@ def main(argv=None, entry=None):
     from gan_control_amd.trainers.generator_trainer import GeneratorTrainer, default_config
     from gan_control_amd.utils.profiling import KernelTimer
 
+    if not args.full:
+        args.no_kernel_timer = args.no_families = args.no_fp32_leg = args.no_host_issue = args.no_cpu_baseline = True
     if cpu_test:
         args.no_kernel_timer = args.no_families = args.no_fp32_leg = args.no_host_issue = True
     elif args.precision:
@@ -463,7 +495,7 @@ def main(argv=None, entry=None):
     trainer = GeneratorTrainer(cfg, device=dev, seed=0)
     real = trainer.synthetic_batch()              # resident in HBM before the timed region
     for red in (trainer.g_reducer, trainer.d_reducer):
-        red.measure = use_dist
+        red.measure = use_dist and args.full
 
     def barrier():
         _sync()
@@ -522,7 +554,7 @@ def main(argv=None, entry=None):
                     'r1': sum(1 for i in timed if i % tc['d_reg_every'] == 0), 'pl': sum(1 for i in timed if i % tc['g_reg_every'] == 0),
                     'cadence': {'r1_every': tc['d_reg_every'], 'pl_every': tc['g_reg_every']}}
     comm = None
-    if use_dist:
+    if use_dist and args.full:
         parts = [red.comm_summary() for red in (trainer.g_reducer, trainer.d_reducer)]
         comm = {'bytes_per_step': sum(c['bytes'] for c in parts) / args.steps, 'exposed_ms_per_step': sum(c['exposed_ms'] for c in parts) / args.steps,
                 'note': 'gradient payload handed to the all-reduce per rank and step; exposed = compute-stream stall at GradientReducer.finish() '
@@ -533,6 +565,8 @@ def main(argv=None, entry=None):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
     stats = trainer.reduced_stats()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(trainer, stats, args.dump_outputs)       # before --full's extra iterations move the weights on
 
     # The same workload once more in exact fp32 arithmetic (the reference's precision): the headline `value` above is the
     # split-bf16 mode (fp32 in HBM, ~16 mantissa bits in the products), so the line carries the fp32 figure next to it.

@@ -35,7 +35,7 @@ def test_gpus_8_weak_scaling_line():
     value = the whole job's images over the slowest rank's time."""
     env = _env()
     env['OMP_NUM_THREADS'] = '1'
-    out = subprocess.run([sys.executable, ENTRY, '--gpus', '8', '--steps', '1', '--warmup', '0', '--size', '16', '--batch-per-gpu', '4', '--no-cpu-baseline'],
+    out = subprocess.run([sys.executable, ENTRY, '--gpus', '8', '--steps', '1', '--warmup', '0', '--size', '16', '--batch-per-gpu', '4', '--no-cpu-baseline', '--full'],
                          env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{')]
@@ -94,10 +94,36 @@ def test_rank_environment_knobs_and_forced_single_rank_ddp():
     assert line['rccl']['knobs'] == {'NCCL_ALGO': 'Ring', 'NCCL_PROTO': None, 'GANCONTROL_BUCKET_MB': '0.25', 'GANCONTROL_LAST_BUCKET_MB': '0.01'}
     assert line['rccl']['buckets']['bucket_bytes'] == 262144 and line['rccl']['buckets']['last_bucket_bytes'] == 10485
     assert line['rccl']['buckets']['generator'] > 8
-    out = subprocess.run([sys.executable, ENTRY, '--force-ddp'] + ARGS, env=_env(), capture_output=True, text=True, timeout=600)
+    out = subprocess.run([sys.executable, ENTRY, '--force-ddp', '--full'] + ARGS, env=_env(), capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith('{')][0])
     assert line['n_gpus'] == 1 and line['rccl']['ranks'] == 1 and line['comm']['bytes_per_step'] > 0
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """Without --full the line carries the headline fields and none of the extras; --dump-outputs writes the parameters and statistics the
+    last timed step left, in float32 / float64 and within 64 MB, and the same arguments give the same files."""
+    import numpy as np
+    runs = []
+    for k in range(2):
+        d = tmp_path / str(k)
+        out = subprocess.run([sys.executable, ENTRY, '--force-ddp', '--dump-outputs', str(d)] + ARGS, env=_env(), capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        runs.append((json.loads([ln for ln in out.stdout.splitlines() if ln.startswith('{')][0]), d))
+    line = runs[0][0]
+    assert line['higher_is_better'] is True and line['unit'] == 'images/sec' and line['dtype'] == 'emulated' and line['steps'] == 2
+    assert abs(line['value'] - 2 * 4 / (line['ms_per_step'] * 2e-3)) < 1e-6 * line['value']
+    assert not {'comm', 'roofline', 'kernels', 'families', 'step_roofline', 'fp32_exact', 'host_issue', 'cpu_baseline'} & line.keys()
+    names = sorted(p.name for p in runs[0][1].iterdir())
+    assert {'generator.npy', 'discriminator.npy', 'g_ema.npy', 'loss_d_loss.npy', 'loss_g_adv_loss.npy'} <= set(names)
+    assert names == sorted(p.name for p in runs[1][1].iterdir())
+    total = 0
+    for n in names:
+        a, b = np.load(runs[0][1] / n), np.load(runs[1][1] / n)
+        assert a.dtype in (np.float32, np.float64) and a.size > 0 and np.isfinite(a).all(), n
+        np.testing.assert_array_equal(a, b, err_msg=n)
+        total += a.nbytes
+    assert total <= 64 << 20
 
 
 import pytest  # noqa: E402

@@ -9,7 +9,7 @@ O=${1:-gpurun_out/scale}; mkdir -p $O
 : > $O/scale.jsonl
 run() {      # run <tag> <bench.py args...>
     tag=$1; shift
-    python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-fp32-leg "$@" > $O/$tag.json 2> $O/$tag.err
+    python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-fp32-leg "$@" > $O/$tag.json 2> $O/$tag.err
     line=$(tail -n 1 $O/$tag.json)
     [ -n "$line" ] && echo "{\"tag\": \"$tag\", \"line\": $line}" >> $O/scale.jsonl || echo "{\"tag\": \"$tag\", \"line\": null}" >> $O/scale.jsonl
 }
