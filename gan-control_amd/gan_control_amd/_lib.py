@@ -118,6 +118,13 @@ SIGNATURES = {
     'gc_grouped_linear_bwd_w_f32': (_i32, [ctypes.POINTER(GlinGroup), _i32, _i32, _vp]),
     'gc_weight_sq_grouped_f32': (_i32, [ctypes.POINTER(WsqGroup), _i32, _vp]),
     'gc_weight_sq_bwd_grouped_f32': (_i32, [ctypes.POINTER(WsqGroup), _i32, _vp]),
+    'gc_crop_resize_ac_f32': (_i32, [_vp, _vp] + [_i32] * 10 + [_vp]),
+    'gc_affine_prelu_f32': (_i32, [_vp] * 5 + [_i32] * 3 + [_vp]),
+    'gc_affine_prelu_bwd_f32': (_i32, [_vp] * 6 + [_i32, _vp] + [_i32] * 4 + [_vp]),
+    'gc_plane_reduce_f32': (_i32, [_vp, _vp, _vp, _i32, _i32, _f32, _vp]),
+    'gc_se_mlp_f32': (_i32, [_vp] * 5 + [_i32] * 3 + [_vp]),
+    'gc_se_mlp_bwd_f32': (_i32, [_vp] * 6 + [_i32] * 3 + [_f32, _vp]),
+    'gc_se_apply_f32': (_i32, [_vp] * 4 + [_i32] * 6 + [_vp]),
     'gc_weight_layout_grouped_f32': (_i32, [ctypes.POINTER(WLayoutGroup), _i32, _vp]),
     'gc_conv2d_pack_weights_bf16x3_grouped': (_i32, [ctypes.POINTER(WPackGroup), _i32, _vp]),
     'gc_weight_layout_f32': (_i32, [_vp, _vp, _i32, _i32, _i32, ctypes.POINTER(_i64 * 3), ctypes.POINTER(_i64 * 3), _i32, _f32, _vp]),

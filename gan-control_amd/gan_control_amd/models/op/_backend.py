@@ -447,6 +447,93 @@ class HipBackend:
                    'gc_resize_bilinear_f32')
         return out
 
+    # -- the identity predictor of the embedding loss (losses/arc_face.py) ----------------------------------------------------------
+    def crop_resize_ac(self, x, top, left, crop_h, crop_w, out_h, out_w, adjoint=False, in_hw=None):
+        """adjoint=False: [B,C,H,W] -> [B,C,out_h,out_w], bilinear (align_corners=True) resize of the crop at (top, left); adjoint=True: x is
+        the [B,C,out_h,out_w] gradient, the result the [B,C,*in_hw] input gradient (zero outside the crop).  gc_crop_resize_ac_f32."""
+        x = x.contiguous()
+        dev = _lib.require_cuda_f32(x)
+        b, c = x.shape[0], x.shape[1]
+        in_h, in_w = in_hw if adjoint else x.shape[2:]
+        y = torch.empty((b, c, in_h, in_w) if adjoint else (b, c, out_h, out_w), dtype=x.dtype, device=dev)
+        rc = _lib.load().gc_crop_resize_ac_f32(_lib.ptr(x), _lib.ptr(y), b * c, in_h, in_w, top, left, crop_h, crop_w, out_h, out_w, int(bool(adjoint)),
+                                               _lib.stream_of(x))
+        _lib.check(rc, 'gc_crop_resize_ac_f32')
+        return y
+
+    def affine_prelu(self, x, scale, shift, alpha):
+        """prelu(x * scale[c] + shift[c], alpha[c]) over [B,C,*]; scale / shift / alpha may be None.  gc_affine_prelu_f32."""
+        x = x.contiguous()
+        dev = _lib.require_cuda_f32(x, scale, shift, alpha)
+        y = torch.empty_like(x)
+        b, c = x.shape[0], x.shape[1]
+        rc = _lib.load().gc_affine_prelu_f32(_lib.ptr(x), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(alpha), _lib.ptr(y), b, c, x.numel() // max(b * c, 1),
+                                             _lib.stream_of(x))
+        _lib.check(rc, 'gc_affine_prelu_f32')
+        return y
+
+    def affine_prelu_bwd(self, g, x, scale, shift, alpha, g2=None, g2_strided=False):
+        """Input gradient of affine_prelu (x: its input, read with alpha only) [+ g2: dense, or at the even pixels when g2_strided]."""
+        g = g.contiguous()
+        x = None if alpha is None else x.contiguous()
+        g2 = None if g2 is None else g2.contiguous()
+        dev = _lib.require_cuda_f32(g, x, scale, shift, alpha, g2)
+        b, c, h, w = g.shape
+        mode = 0 if g2 is None else (2 if g2_strided else 1)
+        want = (b, c, (h + 1) // 2, (w + 1) // 2) if mode == 2 else tuple(g.shape)
+        if g2 is not None and tuple(g2.shape) != want:
+            raise ValueError('affine_prelu_bwd: second gradient %s, expected %s' % (tuple(g2.shape), want))
+        gx = torch.empty_like(g)
+        rc = _lib.load().gc_affine_prelu_bwd_f32(_lib.ptr(g), _lib.ptr(x), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(alpha), _lib.ptr(g2), mode, _lib.ptr(gx),
+                                                 b, c, h, w, _lib.stream_of(g))
+        _lib.check(rc, 'gc_affine_prelu_bwd_f32')
+        return gx
+
+    def plane_reduce(self, a, b=None, mul=1.0):
+        """[B,C,*] (x [B,C,*]) -> [B,C]: mul * sum over the plane of a (* b).  gc_plane_reduce_f32."""
+        a = a.contiguous()
+        b = None if b is None else b.contiguous()
+        dev = _lib.require_cuda_f32(a, b)
+        out = torch.empty((a.shape[0], a.shape[1]), dtype=a.dtype, device=dev)
+        planes = a.shape[0] * a.shape[1]
+        rc = _lib.load().gc_plane_reduce_f32(_lib.ptr(a), _lib.ptr(b), _lib.ptr(out), planes, a.numel() // max(planes, 1), float(mul), _lib.stream_of(a))
+        _lib.check(rc, 'gc_plane_reduce_f32')
+        return out
+
+    def se_mlp(self, m, fc1, fc2):
+        """m [B,C], fc1 [R,C], fc2 [C,R] -> (z = relu(m @ fc1^T) [B,R], s = sigmoid(z @ fc2^T) [B,C]).  gc_se_mlp_f32."""
+        dev = _lib.require_cuda_f32(m, fc1, fc2)
+        b, c = m.shape
+        r = fc1.shape[0]
+        z = torch.empty((b, r), dtype=m.dtype, device=dev)
+        s = torch.empty((b, c), dtype=m.dtype, device=dev)
+        _lib.check(_lib.load().gc_se_mlp_f32(_lib.ptr(m.contiguous()), _lib.ptr(fc1.contiguous()), _lib.ptr(fc2.contiguous()), _lib.ptr(z), _lib.ptr(s), b, c, r,
+                                             _lib.stream_of(m)), 'gc_se_mlp_f32')
+        return z, s
+
+    def se_mlp_bwd(self, t, s, z, fc1, fc2, mul):
+        """t = dL/ds [B,C] -> mul * dL/dm [B,C].  gc_se_mlp_bwd_f32."""
+        dev = _lib.require_cuda_f32(t, s, z, fc1, fc2)
+        b, c = t.shape
+        gm = torch.empty((b, c), dtype=t.dtype, device=dev)
+        _lib.check(_lib.load().gc_se_mlp_bwd_f32(_lib.ptr(t.contiguous()), _lib.ptr(s.contiguous()), _lib.ptr(z.contiguous()), _lib.ptr(fc1.contiguous()),
+                                                 _lib.ptr(fc2.contiguous()), _lib.ptr(gm), b, c, fc1.shape[0], float(mul), _lib.stream_of(t)), 'gc_se_mlp_bwd_f32')
+        return gm
+
+    def se_apply(self, r, s, shortcut=None, stride=1):
+        """r * s[b,c] + shortcut[:, :, ::stride, ::stride] (shortcut may be None).  gc_se_apply_f32."""
+        r = r.contiguous()
+        sc = None if shortcut is None else shortcut.contiguous()
+        dev = _lib.require_cuda_f32(r, s, sc)
+        b, c, h, w = r.shape
+        out = torch.empty_like(r)
+        sh, sw = (sc.shape[2], sc.shape[3]) if sc is not None else (0, 0)
+        if sc is not None and (sc.shape[0] != b or sc.shape[1] != c):
+            raise ValueError('se_apply: shortcut %s does not match %s' % (tuple(sc.shape), tuple(r.shape)))
+        rc = _lib.load().gc_se_apply_f32(_lib.ptr(r), _lib.ptr(s.contiguous()), _lib.ptr(sc), _lib.ptr(out), b * c, h, w, sh, sw, int(stride), _lib.stream_of(r))
+        _lib.check(rc, 'gc_se_apply_f32')
+        return out
+
     def small_gemm_ok(self, a, b):
         """True when alpha * (a @ b) + beta * bias is taken by gc_small_gemm_f32 (inner extent <= 8, output <= 2^19 elements)."""
         if not (a.is_cuda and b.is_cuda and a.dtype == torch.float32 and b.dtype == torch.float32 and a.dim() == 2 and b.dim() == 2):

@@ -531,6 +531,40 @@ int gc_global_avgpool_f32(const float* x, float* y, int planes, int inner, gc_st
 /* y = mul * bilinear(x) + add, F.interpolate(mode='bilinear', align_corners=False) semantics. */
 int gc_resize_bilinear_f32(const float* x, float* y, int planes, int in_h, int in_w, int out_h, int out_w, float mul, float add, gc_stream_t stream);
 
+/* ---- the identity predictor of the embedding loss (losses/arc_face.py, csrc/arcface.hip): forward and input gradient ---------------- */
+
+/* adjoint = 0: y [planes, out_h, out_w] = F.interpolate(crop, (out_h, out_w), mode='bilinear', align_corners=True) of the crop
+ *   x[p, top:top + crop_h, left:left + crop_w] of x [planes, in_h, in_w] (read in place: an offset and the row pitch in_w).
+ * adjoint = 1: x is the gradient [planes, out_h, out_w] and y the full-size input gradient [planes, in_h, in_w], zero outside the crop;
+ *   one deterministic gather pass (no atomics).  The crop must lie inside the image. */
+int gc_crop_resize_ac_f32(const float* x, float* y, int planes, int in_h, int in_w, int top, int left, int crop_h, int crop_w,
+                          int out_h, int out_w, int adjoint, gc_stream_t stream);
+
+/* y[b,c,:] = prelu(x[b,c,:] * scale[c] + shift[c], alpha[c]); scale / shift / alpha may each be NULL (1, 0, no PReLU). */
+int gc_affine_prelu_f32(const float* x, const float* scale, const float* shift, const float* alpha, float* y, int batch, int channels,
+                        int hw, gc_stream_t stream);
+
+/* Input gradient of gc_affine_prelu_f32: gx = g * scale[c] * (pre > 0 ? 1 : alpha[c]), pre = x * scale[c] + shift[c] (x is read only with
+ * alpha), plus a second incoming gradient g2: g2_mode 0 none, 1 dense [B,C,h,w], 2 [B,C,ceil(h/2),ceil(w/2)] added at the even pixels
+ * (the adjoint of the MaxPool2d(1, 2) subsample). */
+int gc_affine_prelu_bwd_f32(const float* g, const float* x, const float* scale, const float* shift, const float* alpha, const float* g2,
+                            int g2_mode, float* gx, int batch, int channels, int h, int w, gc_stream_t stream);
+
+/* out[p] = mul * sum_i a[p,i] * b[p,i] over planes of `inner` elements (b may be NULL: plain sum); one workgroup per plane, fixed order. */
+int gc_plane_reduce_f32(const float* a, const float* b, float* out, int planes, int inner, float mul, gc_stream_t stream);
+
+/* Squeeze-excitation MLP per sample: z[b,:] = relu(fc1 @ m[b,:]), s[b,:] = sigmoid(fc2 @ z[b,:]); fc1 [red, channels], fc2 [channels, red]
+ * (channels <= 2048, red <= 256). */
+int gc_se_mlp_f32(const float* m, const float* fc1, const float* fc2, float* z, float* s, int batch, int channels, int red, gc_stream_t stream);
+
+/* Its backward from t = dL/ds: gm[b,:] = mul * fc1^T (relu'(z) * (fc2^T (t * s * (1 - s)))). */
+int gc_se_mlp_bwd_f32(const float* t, const float* s, const float* z, const float* fc1, const float* fc2, float* gm, int batch, int channels,
+                      int red, float mul, gc_stream_t stream);
+
+/* out[p, y, x] = r[p, y, x] * s[p] + sc[p, y * sc_stride, x * sc_stride] over planes of h x w; sc [planes, sc_h, sc_w] may be NULL. */
+int gc_se_apply_f32(const float* r, const float* s, const float* sc, float* out, int planes, int h, int w, int sc_h, int sc_w, int sc_stride,
+                    gc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
