@@ -1179,9 +1179,6 @@ extern "C" int gc_conv2d_wgrad_f32(const gc_conv_desc* d, const float* x, const 
 
 // lane groups per element group (see wgrad_reduce_kernel): only where the tensor alone cannot fill the chip and there are splits to share out
 static int reduce_groups(size_t n4, int parts) {
-#ifdef GC_REDUCE_FLAT       // A/B build: one lane per element group everywhere (the round-2 reduce)
-    return 1;
-#endif
     if (n4 >= 256 * 256 || parts < 16) return 1;
     return parts >= 64 ? 16 : 4;
 }

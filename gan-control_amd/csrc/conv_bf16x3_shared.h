@@ -1,9 +1,9 @@
-// Shared by the split-bf16 convolution translation units (conv_bf16x3.hip, conv_s2ws.hip): build knobs, the argument block, the hi / lo split of
+// Shared by the split-bf16 convolution translation units (conv_bf16x3.hip, convt_bf16x3.hip, wgrad_bf16x3.hip, conv_s2ws.hip): build knobs, the argument block, the hi / lo split of
 // eight staged values, LDS-DMA helpers.  Everything sits in an anonymous namespace: each translation unit gets its own copy.
 #pragma once
 #include "conv_common.h"
 
-// The same source builds a second time with -DGC_SINGLE (object conv_bf16.o): plain bf16 arithmetic -- ONE MFMA per product on the
+// conv_bf16x3.hip, convt_bf16x3.hip and wgrad_bf16x3.hip build a second time with -DGC_SINGLE (objects *_single.o): plain bf16 arithmetic -- ONE MFMA per product on the
 // hi parts only (bf16 operands, fp32 accumulate, fp32 in HBM; ~3e-3 relative error per layer, the precision of BASELINE.json's
 // config[1] "bf16").  The lo parts are then neither converted, stored to LDS nor read; entry points gc_conv2d_fused_bf16_packed_f32 /
 // gc_conv2d_wgrad_bf16_f32.  It is never the default nor the parity mode.
@@ -23,14 +23,8 @@
 #ifndef GC_MFMA_PRIO
 #define GC_MFMA_PRIO 2
 #endif
-#ifndef GC_PLAIN_SPLIT
-#define GC_PLAIN_SPLIT 1      // dev knob: 0 = leave the scale-and-split arithmetic to the compiler (it forms packed fp32 instructions)
-#endif
 #ifndef GC_WS_MIN_K
 #define GC_WS_MIN_K 64      // input channels from which the wave-specialised forward kernel takes over
-#endif
-#ifndef GC_WG_XCD
-#define GC_WG_XCD 1          // XCD-aware block order of the weight-gradient kernels (0: hardware order)
 #endif
 #ifndef GC_WS_MIN_K32
 #define GC_WS_MIN_K32 32    // ... and its 32-output-channel variant
@@ -44,48 +38,16 @@
 #ifndef GC_CT_ABL
 #define GC_CT_ABL 0           // dev ablations of convt_fused_bf16x3_kernel (wrong results): 1 no stores, 2 no MFMAs, 4 no global loads, 8 no conversion (a pre-split input)
 #endif
-#ifndef GC_CT_DMA
-#define GC_CT_DMA 0           // 1: convt_fused_bf16x3_kernel copies the pre-split weight slab of a chunk HBM -> LDS by LDS-DMA instead of through registers.
-                              // Measured SLOWER at >= 256 input channels (512 -> 256 @64^2, B = 4: 211 -> 239 us; 256 -> 128 @128^2: 183 -> 191; neutral at <= 128): with
-                              // one weight stage the DMA is issued after the barrier that ends the MFMA phase and its latency is exposed before the next one.
-#endif
-#ifndef GC_WS_DMA_STAGER
-#define GC_WS_DMA_STAGER 0     // 1: the staging waves issue the weight LDS-DMA -- measured SLOWER (512 -> 512 @64^2: 177 -> 203 us): the DMA wait lands on the staging waves' critical path
-#endif
-#ifndef GC_CONVT_NARROW
-#define GC_CONVT_NARROW 1       // 16-column q-tiles where they waste fewer lanes than 32-column ones (0: always 32)
-#endif
 #ifndef GC_WS_SLOTS
 #define GC_WS_SLOTS 256     // workgroups the wave-specialised kernel keeps resident: one per CU
 #endif
 #ifndef GC_WS_STAGER_PRIO
 #define GC_WS_STAGER_PRIO 0
 #endif
-#ifndef GC_CONV_STRIDED
-#define GC_CONV_STRIDED 0   // ... and of conv_bf16x3_kernel's tiles per workgroup: measured neutral (its >= 2048 short-lived workgroups are dispatched in tile order anyway)
-#endif
-#ifndef GC_WG2_STRIDED
-#define GC_WG2_STRIDED 1    // ... and of the stride-2 weight gradient
-#endif
-#ifndef GC_WG_STRIDED
-#define GC_WG_STRIDED 1     // the same for the pixel splits of the stride-1 weight gradient (tiles across the rows, a split's tiles gridDim.z apart)
-#endif
-#ifndef GC_WS_STRIDED
-#define GC_WS_STRIDED 1     // a workgroup's tiles are `groups` apart instead of consecutive (DRAM locality of the resident workgroups)
-#endif
 #ifndef GC_S2_ABL
 #define GC_S2_ABL 0         // dev ablations of conv_bf16x3_kernel at stride 2 (wrong results): 1 the loaded registers are written to LDS as they are -- no scale, no hi / lo
                             // split, no masks: what a PRE-SPLIT input (the producer emitting channel-last bf16 pairs, same bytes) would leave of the staging;
                             // 2 no patch loads and no patch commit at all (weights, fragment reads, MFMAs, stores only)
-#endif
-#ifndef GC_FRAG_PIPE
-#define GC_FRAG_PIPE 1      // conv_bf16x3_kernel (up = 1): fragment reads of the next tap issued before the MFMAs of the current one (0: the compiler's order)
-#endif
-#ifndef GC_WS_XCD
-#define GC_WS_XCD 0           // 1: XCD-aware block order of conv_bf16x3_ws_kernel (see the kernel)
-#endif
-#ifndef GC_WS_EARLY_DMA
-#define GC_WS_EARLY_DMA 1   // conv_bf16x3_ws_kernel: weight slabs requested before a finished tile's stores, counted vmcnt, raw barrier (see the multiplying waves' loop)
 #endif
 #ifndef GC_WS_ABL
 #define GC_WS_ABL 0         // dev ablations of conv_bf16x3_ws_kernel (wrong results): 1 no patch staging, 2 no weight DMA, 4 fragments read once, 8 no stores
@@ -99,27 +61,8 @@
 #define GC_CONV_NT 1
 #endif
 #define GC_CONV_ST_AUX (GC_CONV_NT ? 2 : 0)
-#ifndef GC_WS_SHIFT
-#define GC_WS_SHIFT 0        // 1: patch fragments of the jx > 0 taps by a whole-wave DPP shift of the previous tap's instead of an LDS read: correct (all
-                             // convolution tests) and SLOWER -- 512 -> 512 @64^2 181 -> 216 us, 64 -> 64 @512^2 197 -> 280 (round 4, same box): 16 v_mov_b32_dpp per tap
-                             // on the MULTIPLYING waves (and 20 spilled registers) cost more than the 4 ds_read_b128 they replace
-#endif
-#ifndef GC_WS_DMA_HALF
-#define GC_WS_DMA_HALF 0      // 1: the weight slab is issued by multiplying waves 0..3 only (one per SIMD), so that the partner wave has the matrix pipe meanwhile.  MEASURED NEUTRAL
-                              // (round 6, profiles/ws_dma_half_r06_n.log: every shape within +-2 %): the trace then shows the issuing wave spending 4 260 cycles on its nine LDS-DMA
-                              // instructions (470 each; 166 each when all eight waves issue 4-5) -- the instructions queue behind the staging waves' loads in the CU's one
-                              // vector-memory path, whoever issues them
-#endif
-#ifndef GC_WS_DMA_MID
-#define GC_WS_DMA_MID 0       // 1: weight slab of the next item requested inside the MFMA phase, staggered by wave group (see the multiplying waves' loop).  MEASURED neutral at >= 128
-                              // channels and 3-5 % SLOWER at 32 / 64 (round 6, profiles/ws_dma_mid_r06_n2.log): where the slab is requested does not matter
-#endif
 #ifndef GC_WS_BARE
 #define GC_WS_BARE 1         // reduced epilogues (EPK 1 / 2) of the wave-specialised kernel for launches without bias / noise / activation (0: always the full epilogue)
-#endif
-#ifndef GC_WS_NT_LOAD
-#define GC_WS_NT_LOAD 0      // non-temporal patch loads in the wave-specialised forward kernel: measured SLOWER (dominant kernel 409 -> 386 TF/s, step -2 %):
-                             // every patch is re-read by the other output-channel blocks and by the neighbouring tiles' halos
 #endif
 
 
@@ -147,6 +90,18 @@ struct Bf16Args {
 bool s2ws_eligible(const Bf16Args& a);
 int launch_s2ws(Bf16Args a, hipStream_t s);
 
+// Host functions that cross the units built in BOTH arithmetics: an inline namespace per arithmetic keeps the split and the -DGC_SINGLE
+// definitions apart at link time (callers write the plain name).
+#ifdef GC_SINGLE
+#define GC_ARITH single
+#else
+#define GC_ARITH split
+#endif
+inline namespace GC_ARITH {
+int dispatch_t(const Bf16Args& a, hipStream_t s);       // convt_bf16x3.hip: the transposed 3x3 stride-2 convolution (up = 2, pad' = 2)
+bool wg_eligible(const gc_conv_desc* d);                // wgrad_bf16x3.hip: shapes the split-bf16 weight-gradient kernels take
+}
+
 }  // namespace gcconv
 
 namespace {
@@ -161,9 +116,6 @@ using namespace gcconv;
 // element the compiler spends one conversion per VALUE on the hi parts (it needs each hi back as a float for the lo part) and v_perm to pair
 // them up: 5.2 vector instructions per value in the staging loops (round 5, opcode histogram of the commit phase); from the PAIR the two hi
 // parts come back as floats by one shift and one mask -- 3 per value unscaled, 4 scaled, the same bits.
-#ifndef GC_PAIR_SPLIT
-#define GC_PAIR_SPLIT 1
-#endif
 __device__ __forceinline__ unsigned cvt_pk_bf16(float a, float b) {
     unsigned r;
     asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
@@ -172,7 +124,6 @@ __device__ __forceinline__ unsigned cvt_pk_bf16(float a, float b) {
 
 template <bool SCALED>
 __device__ __forceinline__ void split8s(const float (&v)[8], const float (&sc)[8], uint4* h, uint4* l) {
-#if GC_PAIR_SPLIT && GC_PLAIN_SPLIT
     unsigned hh[4], ll[4];
 #pragma unroll
     for (int q = 0; q < 8; q += 2) {
@@ -190,31 +141,6 @@ __device__ __forceinline__ void split8s(const float (&v)[8], const float (&sc)[8
     }
     *h = make_uint4(hh[0], hh[1], hh[2], hh[3]);
     *l = make_uint4(ll[0], ll[1], ll[2], ll[3]);
-#else
-    bf16x8 hh, ll;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        float f = v[q];
-#if GC_PLAIN_SPLIT
-        if (SCALED) asm("v_mul_f32 %0, %1, %2" : "=v"(f) : "v"(v[q]), "v"(sc[q]));
-#else
-        if (SCALED) f = v[q] * sc[q];
-#endif
-        const __bf16 t = (__bf16)f;
-        hh[q] = t;
-        const float tf = (float)t;
-        float dlo;
-#if GC_PLAIN_SPLIT
-        if (SCALED) asm("v_fma_f32 %0, %1, %2, -%3" : "=v"(dlo) : "v"(v[q]), "v"(sc[q]), "v"(tf));
-        else        asm("v_sub_f32 %0, %1, %2" : "=v"(dlo) : "v"(f), "v"(tf));
-#else
-        dlo = f - tf;
-#endif
-        ll[q] = (__bf16)dlo;
-    }
-    *h = *reinterpret_cast<uint4*>(&hh);
-    *l = *reinterpret_cast<uint4*>(&ll);
-#endif
 }
 
 

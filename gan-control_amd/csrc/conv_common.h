@@ -1,4 +1,4 @@
-// Helpers shared by the fp32 (conv.hip) and split-bf16 (conv_bf16x3.hip) convolution kernels.
+// Helpers shared by the fp32 (conv.hip) and split-bf16 (conv_bf16x3.hip, convt_bf16x3.hip, wgrad_bf16x3.hip, conv_s2ws.hip) convolution kernels.
 #pragma once
 #include "common.h"
 

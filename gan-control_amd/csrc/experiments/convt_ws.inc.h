@@ -1,6 +1,6 @@
-// NOT SHIPPED (moved out of conv_bf16x3.hip in round 6): the wave-specialised form of the transposed 3x3 convolution, built with -DGC_CTWS=1 (whole
+// NOT SHIPPED (moved out of the convolution unit in round 6): the wave-specialised form of the transposed 3x3 convolution, built with -DGC_CTWS=1 (whole
 // (H + 1) x (W + 1) q-space) or -DGC_CTWS=2 (the H x W main region next to convt_edge_bf16x3_kernel: +3 % over the one-role kernel, round 6,
-// profiles/ctws_main_edge_r06_c.log).  The design notes are the comment in front of its include in conv_bf16x3.hip.  Included inside the anonymous namespace.
+// profiles/ctws_main_edge_r06_c.log).  The design notes are the comment in front of its include in convt_bf16x3.hip.  Included inside the anonymous namespace.
 
 template <int WOCB, int TPW>
 struct TWCfg {

@@ -39,14 +39,9 @@ __device__ __forceinline__ float4 ld4(const float* p, long long i, long long n) 
     return make_float4(i < n ? p[i] : 0.f, i + 1 < n ? p[i + 1] : 0.f, i + 2 < n ? p[i + 2] : 0.f, i + 3 < n ? p[i + 3] : 0.f);
 }
 // the wide operand of a narrow / weight-gradient launch (32 channels x 1024^2 per sample) is read exactly once
-#ifndef GC_PW_NT_LOAD
-#define GC_PW_NT_LOAD 0      // measured neutral on the whole step (75.78 vs 75.66 images/s, round 4): off
-#endif
+// (loaded plainly all the same: a non-temporal load measured neutral on the whole step -- DESIGN.md, "Tried and rejected")
 template <bool VEC>
 __device__ __forceinline__ float4 ld4s(const float* p, long long i, long long n) {
-#if GC_PW_NT_LOAD
-    if (VEC) { const gc::f32x4_t t = __builtin_nontemporal_load(reinterpret_cast<const gc::f32x4_t*>(p + i)); return make_float4(t.x, t.y, t.z, t.w); }
-#endif
     return ld4<VEC>(p, i, n);
 }
 template <bool VEC>
