@@ -75,6 +75,29 @@ extern "C" int gc_conv2d_variant_name(const gc_conv_desc* d, int mode, char* nam
     return rc;
 }
 
+extern "C" int gc_conv2d_wgrad_variant_name(const gc_conv_desc* d, int mode, int samples, char* name, int name_bytes) {
+    if (!d || !name || name_bytes < 128) return gc::fail(GC_ERR_BAD_ARG, "gc_conv2d_wgrad_variant_name: null pointer or fewer than 128 bytes");
+    if (mode < 0 || mode > 2) return gc::fail(GC_ERR_BAD_ARG, "gc_conv2d_wgrad_variant_name: mode %d (0 = fp32, 1 = split-bf16, 2 = plain bf16)", mode);
+    name[0] = 0;
+    alignas(16) static float dummy[4];          // 16-byte aligned as the tensors of a caller are; never dereferenced: the launchers return before any launch while probing
+    void* ws = reinterpret_cast<void*>(uintptr_t(16));
+    // the workspace a caller sizes with the queries: the launchers check it before they choose
+    const size_t wb = samples ? gc_conv2d_wgrad_samples_workspace(d, mode) : (mode == 0 ? gc_conv2d_wgrad_workspace(d) : gc_conv2d_wgrad_bf16x3_workspace(d));
+    gc::probe_buf() = name;
+    int rc;
+    if (samples) {
+        rc = mode == 0 ? gc_conv2d_wgrad_samples_f32(d, dummy, dummy, nullptr, nullptr, dummy, dummy, ws, wb, nullptr)
+           : mode == 1 ? gc_conv2d_wgrad_samples_bf16x3_f32(d, dummy, dummy, nullptr, nullptr, dummy, dummy, ws, wb, nullptr)
+                       : gc_conv2d_wgrad_samples_bf16_f32(d, dummy, dummy, nullptr, nullptr, dummy, dummy, ws, wb, nullptr);
+    } else {
+        rc = mode == 0 ? gc_conv2d_wgrad_f32(d, dummy, dummy, nullptr, nullptr, dummy, ws, wb, nullptr)
+           : mode == 1 ? gc_conv2d_wgrad_bf16x3_f32(d, dummy, dummy, nullptr, nullptr, dummy, ws, wb, nullptr)
+                       : gc_conv2d_wgrad_bf16_f32(d, dummy, dummy, nullptr, nullptr, dummy, ws, wb, nullptr);
+    }
+    gc::probe_buf() = nullptr;
+    return rc;
+}
+
 extern "C" int gc_abi_version(void) { return GC_ABI_VERSION; }
 extern "C" int gc_struct_sizes(size_t* sizes, int n) {
     const size_t all[GC_STRUCT_COUNT] = {sizeof(gc_conv_desc), sizeof(gc_conv_epilogue), sizeof(gc_wlayout_group),

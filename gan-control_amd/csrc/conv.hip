@@ -1018,14 +1018,15 @@ int launch_wgrad_small(const gc_conv_desc* d, const float* x, const float* dy, c
     const size_t lds = wgs_lds_bytes(d, bg);
     const dim3 grid(gc::ceil_div(d->in_ch, 32), gc::ceil_div(d->out_ch, 32));
     const int chunks = plane <= 64 ? 1 : (plane <= 128 ? 2 : 5);
-    static bool done[6][16] = {{false}};
+    if (gc::probing()) return gc::probe_name("wgrad_f32_small_kernel<%d,%d>|down%d,k3|plan:groups=%d,direct", d->down, chunks, d->down, gc::ceil_div(d->batch, bg));
+    static bool done[5][16] = {{false}};
 #define GC_WGS_LAUNCH(DOWN_, J_, SLOT_)                                                                                                                   \
     do {                                                                                                                                                \
         if (int rc = gc::allow_dynamic_lds(reinterpret_cast<const void*>(&wgrad_f32_small_kernel<DOWN_, J_>), small_lds_max(), done[SLOT_], "gc_conv2d_wgrad_f32(small planes)")) return rc; \
         hipLaunchKernelGGL((wgrad_f32_small_kernel<DOWN_, J_>), grid, dim3(WGS_THREADS), lds, s, q);                                                    \
     } while (0)
     if (d->down == 2) { if (chunks == 1) GC_WGS_LAUNCH(2, 1, 0); else if (chunks == 2) GC_WGS_LAUNCH(2, 2, 1); else GC_WGS_LAUNCH(2, 5, 2); }
-    else              { if (chunks == 1) GC_WGS_LAUNCH(1, 1, 3); else if (chunks == 2) GC_WGS_LAUNCH(1, 2, 4); else GC_WGS_LAUNCH(1, 5, 5); }
+    else              { if (chunks == 1) GC_WGS_LAUNCH(1, 1, 3); else GC_WGS_LAUNCH(1, 2, 4); }       // stride 1: the padded plane is at most 10 x 10 (wgrad_small_eligible), never five chunks
 #undef GC_WGS_LAUNCH
     return gc::check_launch("gc_conv2d_wgrad_f32(small planes)");
 }
@@ -1034,6 +1035,11 @@ template <int DOWN, int KS>
 int dispatch_wgrad(const WgradArgs& a, const WgradPlan& pl, hipStream_t s) {
     dim3 grid(gc::ceil_div(a.K, pl.kt), gc::ceil_div(a.N, pl.nt), pl.splits);
     constexpr bool narrow = DOWN == 2 || KS == 3;
+    if (gc::probing()) {
+        static const char* const cfgs[4] = {narrow ? "2,2,1,1" : "2,2,1,2", "1,2,2,2", "2,1,2,2", "1,1,4,4"};
+        return gc::probe_name("wgrad_mfma_kernel<%s,%d,%d>|down%d,k%d|plan:splits=%d,tiles_per_split=%d%s", cfgs[pl.cfg < 3 ? pl.cfg : 3], DOWN, KS, DOWN, KS,
+                              pl.splits, pl.tiles_per_split, pl.parts == 1 ? ",direct" : "");
+    }
     switch (pl.cfg) {
         case 0: hipLaunchKernelGGL((wgrad_mfma_kernel<2, 2, 1, (narrow ? 1 : 2), DOWN, KS>), grid, dim3(256), 0, s, a); break;
         case 1: hipLaunchKernelGGL((wgrad_mfma_kernel<1, 2, 2, 2, DOWN, KS>), grid, dim3(256), 0, s, a); break;
@@ -1160,6 +1166,7 @@ extern "C" int gc_conv2d_wgrad_f32(const gc_conv_desc* d, const float* x, const 
     hipStream_t s = (hipStream_t)stream;
     const size_t count = (size_t)d->kh * d->kw * d->in_ch * d->out_ch;
     if (d->batch == 0) {
+        if (gc::probing()) return gc::probe_name("hipMemsetAsync|empty batch");
         hipError_t e = hipMemsetAsync(dw, 0, count * sizeof(float), s);
         return e == hipSuccess ? GC_OK : gc::fail(GC_ERR_HIP, "gc_conv2d_wgrad_f32: memset: %s", hipGetErrorString(e));
     }
@@ -1172,7 +1179,7 @@ extern "C" int gc_conv2d_wgrad_f32(const gc_conv_desc* d, const float* x, const 
                 d->out_h, d->out_w, d->pad_y, d->pad_x, pl.tiles_x, pl.tiles_y, pl.tiles_per_split};
     if (d->kh == 3) rc = d->down == 2 ? dispatch_wgrad<2, 3>(a, pl, s) : dispatch_wgrad<1, 3>(a, pl, s);
     else            rc = d->down == 2 ? dispatch_wgrad<2, 1>(a, pl, s) : dispatch_wgrad<1, 1>(a, pl, s);
-    if (rc) return rc;
+    if (rc || gc::probing()) return rc;       // probing: the name is written, nothing was launched and nothing is reduced
     if (pl.parts == 1) return GC_OK;
     return launch_wgrad_reduce(static_cast<const float*>(workspace), dw, count, pl.parts, s);
 }

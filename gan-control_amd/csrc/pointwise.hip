@@ -322,6 +322,7 @@ int gcconv::pointwise_wgrad(const gc_conv_desc* d, const float* x, const float* 
     a.groups_per_block = (int)(((a.plane + 3) / 4 + blocks - 1) / blocks);
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(blocks, d->batch, (a.L + CHUNK - 1) / CHUNK);
+    if (gc::probing()) return gc::probe_name("pw_wgrad_kernel<%s>|thin_%s|down1,k1%s|plan:blocks=%d", a.vec ? "true" : "false", thin_is_x ? "x" : "dy", dw_samples ? "|samples" : "", blocks);
     if (a.vec) hipLaunchKernelGGL(pw_wgrad_kernel<true>, grid, dim3(256), 0, s, a);
     else       hipLaunchKernelGGL(pw_wgrad_kernel<false>, grid, dim3(256), 0, s, a);
     int rc = gc::check_launch("gc_conv2d_wgrad_f32(pointwise)");

@@ -968,6 +968,15 @@ int wgrad_launch(const gc_conv_desc* d, const float* x, const float* dy, const f
              d->in_h, d->in_w, d->out_h, d->out_w, d->pad_y, d->pad_x, pl.tiles_x, pl.tiles_y, pl.tiles_per_split, d->in_pitch ? d->in_pitch : d->in_w,
              dw_samples ? pl.splits / d->batch : 0};
     dim3 grid(gc::ceil_div(d->in_ch, pl.kt), gc::ceil_div(d->out_ch, pl.ct), pl.splits);
+    // dispatch probe (gc_conv2d_wgrad_variant_name): "<kernel<template arguments, %d = taps>>|down,k[|samples]|plan:<split plan>"; everything in front of
+    // "|plan:" names the code that runs, the plan says how the pixel tiles are dealt to the splits and whether the reduce pass is skipped
+    auto probe = [&](const char* kernel_fmt, int bands) {
+        char kernel[64], extra[24] = "";
+        snprintf(kernel, sizeof kernel, kernel_fmt, d->kh);
+        if (bands) snprintf(extra, sizeof extra, ",bands=%d", bands);
+        return gc::probe_name("%s|down%d,k%d%s|plan:splits=%d,tiles_per_split=%d%s%s", kernel, d->down, d->kh, dw_samples ? "|samples" : "",
+                              pl.splits, pl.tiles_per_split, extra, direct ? ",direct" : "");
+    };
 #if GC_WG_WS
     // the wave-specialised kernel: 3 x 3 "same" convolutions with whole 64-channel blocks on both sides; strips of rb rows, at least two per split
     if (d->down == 1 && d->kh == 3 && !pl.small && d->in_ch % 64 == 0 && d->out_ch % 64 == 0 && d->pad_x == 1 && d->pad_y == 1 && d->out_w >= 32 &&
@@ -976,7 +985,7 @@ int wgrad_launch(const gc_conv_desc* d, const float* x, const float* dy, const f
         const long long pool = (long long)pl.tiles_x * (dw_samples ? 1 : d->batch);          // ... strips per row band in that pool
         const int rb = (d->out_h % 16 == 0 && pool * (d->out_h / 16) >= 2LL * per) ? 16 : 0;
         if (rb) {
-            if (gc::probing()) return gc::probe_name("wgrad_bf16x3_ws_kernel|rb%d", rb);
+            if (gc::probing()) return probe("wgrad_bf16x3_ws2_kernel", d->out_h / rb);
             hipLaunchKernelGGL(wgrad_bf16x3_ws2_kernel, grid, dim3(1024), 0, s, a, d->out_h / rb);
             int rc = gc::check_launch(who);
             if (rc || direct) return rc;
@@ -987,22 +996,26 @@ int wgrad_launch(const gc_conv_desc* d, const float* x, const float* dy, const f
 #endif
     if (d->down == 2) {
         if (pl.ct == 128) {
-            if (gc::probing()) return gc::probe_name("wgrad_bf16x3_s2_kernel<1,%d,1,4>", d->kh);
+            if (gc::probing()) return probe("wgrad_bf16x3_s2_kernel<1,%d,1,4>", 0);
             if (d->kh == 3) hipLaunchKernelGGL((wgrad_bf16x3_s2_kernel<1, 3, 1, 4>), grid, dim3(256), 0, s, a);
             else            hipLaunchKernelGGL((wgrad_bf16x3_s2_kernel<1, 1, 1, 4>), grid, dim3(256), 0, s, a);
         } else if (pl.kt == 32) {
+            if (gc::probing()) return probe("wgrad_bf16x3_s2_kernel<2,%d,1>", 0);
             if (d->kh == 3) hipLaunchKernelGGL((wgrad_bf16x3_s2_kernel<2, 3, 1>), grid, dim3(256), 0, s, a);
             else            hipLaunchKernelGGL((wgrad_bf16x3_s2_kernel<2, 1, 1>), grid, dim3(256), 0, s, a);
         } else if (pl.tr == 1) {
+            if (gc::probing()) return probe("wgrad_bf16x3_s2_kernel<1,%d,2>", 0);
             if (d->kh == 3) hipLaunchKernelGGL((wgrad_bf16x3_s2_kernel<1, 3, 2>), grid, dim3(256), 0, s, a);
             else            hipLaunchKernelGGL((wgrad_bf16x3_s2_kernel<1, 1, 2>), grid, dim3(256), 0, s, a);
         } else {
             return gc::fail(GC_ERR_UNSUPPORTED, "%s: no stride-2 kernel for this tile plan", who);
         }
     } else if (pl.small) {
+        if (gc::probing()) return probe("wgrad_bf16x3_kernel<1,1,4,6,%d>", 0);
         if (d->kh == 3) hipLaunchKernelGGL((wgrad_bf16x3_kernel<1, 1, 4, 6, 3>), grid, dim3(256), 0, s, a);
         else            hipLaunchKernelGGL((wgrad_bf16x3_kernel<1, 1, 4, 6, 1>), grid, dim3(256), 0, s, a);
     } else {
+        if (gc::probing()) return probe("wgrad_bf16x3_kernel<2,2,1,2,%d>", 0);
 #if defined(GC_ABL)      // dev ablation: GC_ABL_DYNLDS=<bytes> of dynamic LDS forces one workgroup per CU
         static const int dyn = getenv("GC_ABL_DYNLDS") ? atoi(getenv("GC_ABL_DYNLDS")) : 0;
         if (dyn > 0 && d->kh == 3) {

@@ -35,6 +35,22 @@ def conv_variant(geom, n_out, batch=1, k_in=64, mode='f32', in_hw=None):
     return name
 
 
+def wgrad_variant(geom, n_out, batch, k_in, mode, in_hw, samples=False):
+    """Name of the kernel variant the weight-gradient dispatch selects for this shape (gc_conv2d_wgrad_variant_name: the launchers of
+    gc_conv2d_wgrad_* -- with samples=True of gc_conv2d_wgrad_samples_* -- run in the same no-launch probe mode):
+    '<kernel<template arguments>>|down<d>,k<taps>[|samples]|plan:<split plan>'."""
+    import ctypes
+    from .. import _lib
+    key = ('wgrad', tuple(geom), n_out, batch, k_in, mode, tuple(in_hw), bool(samples))
+    name = _VARIANTS.get(key)
+    if name is None:
+        desc = _lib.ConvDesc(batch, k_in, n_out, in_hw[0], in_hw[1], geom.out_h, geom.out_w, geom.kh, geom.kw, geom.up, geom.down, geom.pad_y, geom.pad_x)
+        buf = ctypes.create_string_buffer(128)
+        _lib.check(_lib.load().gc_conv2d_wgrad_variant_name(desc, _MODES[mode], int(bool(samples)), buf, 128), 'gc_conv2d_wgrad_variant_name')
+        name = _VARIANTS[key] = buf.value.decode()
+    return name
+
+
 def conv_flops(batch, k_in, n_out, in_h, in_w, geom):
     px = in_h * in_w if geom.up > 1 else geom.out_h * geom.out_w
     return 2.0 * batch * k_in * n_out * geom.kh * geom.kw * px

@@ -360,6 +360,18 @@ int gc_conv2d_wgrad_bf16_f32(const gc_conv_desc* d, const float* x, const float*
                              const float* in_scale, const float* out_scale, float* dw,
                              void* workspace, size_t workspace_bytes, gc_stream_t stream);
 
+/* Name of the kernel variant the WEIGHT-GRADIENT dispatchers pick for a shape, written by the dispatch code itself as
+ * gc_conv2d_variant_name does for the forward direction (no launch, no GPU needed):
+ *
+ *   "<kernel<template arguments>>|down<d>,k<taps>[|samples]|plan:<how the pixels are split>"
+ *
+ * e.g. "wgrad_bf16x3_s2_kernel<1,3,1,4>|down2,k3|plan:splits=64,tiles_per_split=33".  The part in front of "|plan:" names the code
+ * that runs; the plan holds the split count, the tiles (wgrad_bf16x3_ws2_kernel: 16-row strips) per split, that kernel's row bands
+ * ("bands=") and ",direct" when the kernel writes dw itself instead of partial sums for a reduce pass.
+ * mode: 0 = exact fp32, 1 = split-bf16, 2 = plain bf16.  samples != 0: the gc_conv2d_wgrad_samples_* entry point of that mode
+ * (GC_ERR_UNSUPPORTED where the shape has no per-sample form).  name must hold >= 128 bytes. */
+int gc_conv2d_wgrad_variant_name(const gc_conv_desc* d, int mode, int samples, char* name, int name_bytes);
+
 /* Weight gradient together with each sample's share of it:
  *
  *   dw_samples[b,ty,tx,k,n] = in_scale[b,k] * out_scale[b,n] * sum_{oy,ox} x[b,k, oy*down + ty - pad_y, ...] * dy[b,n,oy,ox]

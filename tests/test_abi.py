@@ -44,6 +44,13 @@ def test_argument_validation_without_gpu():
     assert lib.gc_conv2d_f32(d, 1, 1, None, None, 1, None) == -2          # up = down = 2
     assert lib.gc_conv2d_wgrad_workspace(_lib.ConvDesc(4, 512, 512, 64, 64, 64, 64, 3, 3, 1, 1, 1, 1)) > 0
     assert lib.gc_bias_act_f32(1, None, 1, None, 1, 1, 1, 1, 0.2, 1.0, None) == -1   # noise without weight
+    d = _lib.ConvDesc(4, 512, 512, 64, 64, 64, 64, 3, 3, 1, 1, 1, 1)
+    name = ctypes.create_string_buffer(128)
+    assert lib.gc_conv2d_wgrad_variant_name(d, 1, 0, name, 64) == -1            # a name needs 128 bytes
+    assert lib.gc_conv2d_wgrad_variant_name(d, 3, 0, name, 128) == -1           # no such arithmetic mode
+    assert lib.gc_conv2d_wgrad_variant_name(None, 1, 0, name, 128) == -1
+    assert lib.gc_conv2d_wgrad_variant_name(d, 0, 1, name, 128) == -2           # fp32 arithmetic: no per-sample form for this shape
+    assert lib.gc_conv2d_wgrad_variant_name(d, 1, 0, name, 128) == 0 and name.value.startswith(b'wgrad_bf16x3_')     # ... and nothing was launched
 
 
 def test_missing_library_fails_loudly(monkeypatch):

@@ -14,7 +14,7 @@ sys.path.insert(0, os.path.join(REPO, 'gan-control_amd'))
 
 from gan_control_amd import _lib                                        # noqa: E402
 from gan_control_amd.models.op._backend import ConvGeom                 # noqa: E402
-from gan_control_amd.utils.profiling import conv_variant                # noqa: E402
+from gan_control_amd.utils.profiling import conv_variant, wgrad_variant   # noqa: E402
 
 
 def _out(n, k, up, down, pad):
@@ -85,3 +85,199 @@ def test_split_workspace_covers_the_slices():
     per_slice = b * N * o * o * 4
     assert slices > 0 and slices % per_slice == 0 and 2 <= slices // per_slice <= K // 64
     assert lib.gc_conv2d_bf16x3_workspace(desc) >= lib.gc_conv2d_bf16x3_packed_bytes(desc) + slices
+
+
+# ---- weight gradients (gc_conv2d_wgrad_variant_name: the same no-launch probe through the launchers of gc_conv2d_wgrad_* / gc_conv2d_wgrad_samples_*) ----
+
+def _wprobe(b, K, N, h, k, down, pad, samples=False, mode='bf16x3', w=None):
+    w = h if w is None else w
+    geom = ConvGeom(k, k, 1, down, pad, pad, (h + 2 * pad - k) // down + 1, (w + 2 * pad - k) // down + 1)
+    return wgrad_variant(geom, N, b, K, mode, (h, w), samples)
+
+
+def _kernel(name):
+    """A variant name without its split plan: the code that runs."""
+    return name.split('|plan:')[0]
+
+
+# (batch, K, N, plane, taps, down, pad, per-sample form) -> kernel name prefix, split-bf16 arithmetic at B = 4 and B = 8.  In order: the 3x3 stride-1 layers of
+# G and D (G's also in the per-sample form its first-order backward takes) and D's 513 -> 512 layer; D's stride-2 3x3 layers with their 1x1 stride-2 skips; the
+# transposed layers of G, whose weight gradient is the stride-2 one with the operands swapped; ToRGB at every resolution and FromRGB.  Names derived from the
+# built library, then frozen.
+STEP_WGRAD_SHAPES = [
+    ((4, 512, 512, 4, 3, 1, 1, False), 'wgrad_f32_small_kernel<1,1>|down1,k3'),
+    ((8, 512, 512, 4, 3, 1, 1, False), 'wgrad_f32_small_kernel<1,1>|down1,k3'),
+    ((4, 512, 512, 4, 3, 1, 1, True), 'wgrad_bf16x3_kernel<2,2,1,2,3>|down1,k3|samples'),
+    ((8, 512, 512, 4, 3, 1, 1, True), 'wgrad_bf16x3_kernel<2,2,1,2,3>|down1,k3|samples'),
+    ((4, 512, 512, 8, 3, 1, 1, False), 'wgrad_f32_small_kernel<1,2>|down1,k3'),
+    ((8, 512, 512, 8, 3, 1, 1, False), 'wgrad_f32_small_kernel<1,2>|down1,k3'),
+    ((4, 512, 512, 8, 3, 1, 1, True), 'wgrad_bf16x3_kernel<2,2,1,2,3>|down1,k3|samples'),
+    ((8, 512, 512, 8, 3, 1, 1, True), 'wgrad_bf16x3_kernel<2,2,1,2,3>|down1,k3|samples'),
+    ((4, 512, 512, 16, 3, 1, 1, False), 'wgrad_bf16x3_kernel<2,2,1,2,3>|down1,k3'),
+    ((8, 512, 512, 16, 3, 1, 1, False), 'wgrad_bf16x3_kernel<2,2,1,2,3>|down1,k3'),
+    ((4, 512, 512, 16, 3, 1, 1, True), 'wgrad_bf16x3_kernel<2,2,1,2,3>|down1,k3|samples'),
+    ((8, 512, 512, 16, 3, 1, 1, True), 'wgrad_bf16x3_kernel<2,2,1,2,3>|down1,k3|samples'),
+    ((4, 512, 512, 32, 3, 1, 1, False), 'wgrad_bf16x3_ws2_kernel|down1,k3'),
+    ((8, 512, 512, 32, 3, 1, 1, False), 'wgrad_bf16x3_ws2_kernel|down1,k3'),
+    ((4, 512, 512, 32, 3, 1, 1, True), 'wgrad_bf16x3_kernel<2,2,1,2,3>|down1,k3|samples'),
+    ((8, 512, 512, 32, 3, 1, 1, True), 'wgrad_bf16x3_ws2_kernel|down1,k3|samples'),
+    ((4, 512, 512, 64, 3, 1, 1, False), 'wgrad_bf16x3_ws2_kernel|down1,k3'),
+    ((8, 512, 512, 64, 3, 1, 1, False), 'wgrad_bf16x3_ws2_kernel|down1,k3'),
+    ((4, 512, 512, 64, 3, 1, 1, True), 'wgrad_bf16x3_ws2_kernel|down1,k3|samples'),
+    ((8, 512, 512, 64, 3, 1, 1, True), 'wgrad_bf16x3_ws2_kernel|down1,k3|samples'),
+    ((4, 256, 256, 128, 3, 1, 1, False), 'wgrad_bf16x3_ws2_kernel|down1,k3'),
+    ((8, 256, 256, 128, 3, 1, 1, False), 'wgrad_bf16x3_ws2_kernel|down1,k3'),
+    ((4, 256, 256, 128, 3, 1, 1, True), 'wgrad_bf16x3_ws2_kernel|down1,k3|samples'),
+    ((8, 256, 256, 128, 3, 1, 1, True), 'wgrad_bf16x3_ws2_kernel|down1,k3|samples'),
+    ((4, 128, 128, 256, 3, 1, 1, False), 'wgrad_bf16x3_ws2_kernel|down1,k3'),
+    ((8, 128, 128, 256, 3, 1, 1, False), 'wgrad_bf16x3_ws2_kernel|down1,k3'),
+    ((4, 128, 128, 256, 3, 1, 1, True), 'wgrad_bf16x3_ws2_kernel|down1,k3|samples'),
+    ((8, 128, 128, 256, 3, 1, 1, True), 'wgrad_bf16x3_ws2_kernel|down1,k3|samples'),
+    ((4, 64, 64, 512, 3, 1, 1, False), 'wgrad_bf16x3_ws2_kernel|down1,k3'),
+    ((8, 64, 64, 512, 3, 1, 1, False), 'wgrad_bf16x3_ws2_kernel|down1,k3'),
+    ((4, 64, 64, 512, 3, 1, 1, True), 'wgrad_bf16x3_ws2_kernel|down1,k3|samples'),
+    ((8, 64, 64, 512, 3, 1, 1, True), 'wgrad_bf16x3_ws2_kernel|down1,k3|samples'),
+    ((4, 32, 32, 1024, 3, 1, 1, False), 'wgrad_bf16x3_kernel<1,1,4,6,3>|down1,k3'),
+    ((8, 32, 32, 1024, 3, 1, 1, False), 'wgrad_bf16x3_kernel<1,1,4,6,3>|down1,k3'),
+    ((4, 32, 32, 1024, 3, 1, 1, True), 'wgrad_bf16x3_kernel<1,1,4,6,3>|down1,k3|samples'),
+    ((8, 32, 32, 1024, 3, 1, 1, True), 'wgrad_bf16x3_kernel<1,1,4,6,3>|down1,k3|samples'),
+    ((4, 513, 512, 4, 3, 1, 1, False), 'wgrad_f32_small_kernel<1,1>|down1,k3'),
+    ((8, 513, 512, 4, 3, 1, 1, False), 'wgrad_f32_small_kernel<1,1>|down1,k3'),
+    ((4, 32, 64, 1025, 3, 2, 0, False), 'wgrad_bf16x3_s2_kernel<2,3,1>|down2,k3'),
+    ((8, 32, 64, 1025, 3, 2, 0, False), 'wgrad_bf16x3_s2_kernel<2,3,1>|down2,k3'),
+    ((4, 32, 64, 1024, 1, 2, 0, False), 'wgrad_bf16x3_s2_kernel<2,1,1>|down2,k1'),
+    ((8, 32, 64, 1024, 1, 2, 0, False), 'wgrad_bf16x3_s2_kernel<2,1,1>|down2,k1'),
+    ((4, 64, 128, 513, 3, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,3,1,4>|down2,k3'),
+    ((8, 64, 128, 513, 3, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,3,1,4>|down2,k3'),
+    ((4, 64, 128, 512, 1, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,1,1,4>|down2,k1'),
+    ((8, 64, 128, 512, 1, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,1,1,4>|down2,k1'),
+    ((4, 128, 256, 257, 3, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,3,1,4>|down2,k3'),
+    ((8, 128, 256, 257, 3, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,3,1,4>|down2,k3'),
+    ((4, 128, 256, 256, 1, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,1,1,4>|down2,k1'),
+    ((8, 128, 256, 256, 1, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,1,1,4>|down2,k1'),
+    ((4, 256, 512, 129, 3, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,3,1,4>|down2,k3'),
+    ((8, 256, 512, 129, 3, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,3,1,4>|down2,k3'),
+    ((4, 256, 512, 128, 1, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,1,1,4>|down2,k1'),
+    ((8, 256, 512, 128, 1, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,1,1,4>|down2,k1'),
+    ((4, 512, 512, 65, 3, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,3,1,4>|down2,k3'),
+    ((8, 512, 512, 65, 3, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,3,1,4>|down2,k3'),
+    ((4, 512, 512, 64, 1, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,1,1,4>|down2,k1'),
+    ((8, 512, 512, 64, 1, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,1,1,4>|down2,k1'),
+    ((4, 512, 512, 33, 3, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,3,1,4>|down2,k3'),
+    ((8, 512, 512, 33, 3, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,3,1,4>|down2,k3'),
+    ((4, 512, 512, 32, 1, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,1,1,4>|down2,k1'),
+    ((8, 512, 512, 32, 1, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,1,1,4>|down2,k1'),
+    ((4, 512, 512, 17, 3, 2, 0, False), 'wgrad_f32_small_kernel<2,5>|down2,k3'),
+    ((8, 512, 512, 17, 3, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,3,1,4>|down2,k3'),
+    ((4, 512, 512, 16, 1, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,1,1,4>|down2,k1'),
+    ((8, 512, 512, 16, 1, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,1,1,4>|down2,k1'),
+    ((4, 512, 512, 9, 3, 2, 0, False), 'wgrad_f32_small_kernel<2,2>|down2,k3'),
+    ((8, 512, 512, 9, 3, 2, 0, False), 'wgrad_f32_small_kernel<2,2>|down2,k3'),
+    ((4, 512, 512, 8, 1, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,1,1,4>|down2,k1'),
+    ((8, 512, 512, 8, 1, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,1,1,4>|down2,k1'),
+    ((4, 64, 32, 1025, 3, 2, 0, False), 'wgrad_mfma_kernel<2,1,2,2,2,3>|down2,k3'),
+    ((8, 64, 32, 1025, 3, 2, 0, False), 'wgrad_mfma_kernel<2,1,2,2,2,3>|down2,k3'),
+    ((4, 128, 64, 513, 3, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,3,2>|down2,k3'),
+    ((8, 128, 64, 513, 3, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,3,2>|down2,k3'),
+    ((4, 128, 64, 513, 3, 2, 0, True), 'wgrad_bf16x3_s2_kernel<1,3,2>|down2,k3|samples'),
+    ((8, 128, 64, 513, 3, 2, 0, True), 'wgrad_bf16x3_s2_kernel<1,3,2>|down2,k3|samples'),
+    ((4, 256, 128, 257, 3, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,3,1,4>|down2,k3'),
+    ((8, 256, 128, 257, 3, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,3,1,4>|down2,k3'),
+    ((4, 256, 128, 257, 3, 2, 0, True), 'wgrad_bf16x3_s2_kernel<1,3,1,4>|down2,k3|samples'),
+    ((8, 256, 128, 257, 3, 2, 0, True), 'wgrad_bf16x3_s2_kernel<1,3,1,4>|down2,k3|samples'),
+    ((4, 512, 256, 129, 3, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,3,1,4>|down2,k3'),
+    ((8, 512, 256, 129, 3, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,3,1,4>|down2,k3'),
+    ((4, 512, 256, 129, 3, 2, 0, True), 'wgrad_bf16x3_s2_kernel<1,3,1,4>|down2,k3|samples'),
+    ((8, 512, 256, 129, 3, 2, 0, True), 'wgrad_bf16x3_s2_kernel<1,3,1,4>|down2,k3|samples'),
+    ((4, 512, 512, 65, 3, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,3,1,4>|down2,k3'),
+    ((8, 512, 512, 65, 3, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,3,1,4>|down2,k3'),
+    ((4, 512, 512, 65, 3, 2, 0, True), 'wgrad_bf16x3_s2_kernel<1,3,1,4>|down2,k3|samples'),
+    ((8, 512, 512, 65, 3, 2, 0, True), 'wgrad_bf16x3_s2_kernel<1,3,1,4>|down2,k3|samples'),
+    ((4, 512, 512, 33, 3, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,3,1,4>|down2,k3'),
+    ((8, 512, 512, 33, 3, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,3,1,4>|down2,k3'),
+    ((4, 512, 512, 33, 3, 2, 0, True), 'wgrad_bf16x3_s2_kernel<1,3,1,4>|down2,k3|samples'),
+    ((8, 512, 512, 33, 3, 2, 0, True), 'wgrad_bf16x3_s2_kernel<1,3,1,4>|down2,k3|samples'),
+    ((4, 512, 512, 17, 3, 2, 0, False), 'wgrad_f32_small_kernel<2,5>|down2,k3'),
+    ((8, 512, 512, 17, 3, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,3,1,4>|down2,k3'),
+    ((4, 512, 512, 17, 3, 2, 0, True), 'wgrad_bf16x3_s2_kernel<1,3,1,4>|down2,k3|samples'),
+    ((8, 512, 512, 17, 3, 2, 0, True), 'wgrad_bf16x3_s2_kernel<1,3,1,4>|down2,k3|samples'),
+    ((4, 512, 512, 9, 3, 2, 0, False), 'wgrad_f32_small_kernel<2,2>|down2,k3'),
+    ((8, 512, 512, 9, 3, 2, 0, False), 'wgrad_f32_small_kernel<2,2>|down2,k3'),
+    ((4, 512, 512, 9, 3, 2, 0, True), 'wgrad_bf16x3_s2_kernel<1,3,1,4>|down2,k3|samples'),
+    ((8, 512, 512, 9, 3, 2, 0, True), 'wgrad_bf16x3_s2_kernel<1,3,1,4>|down2,k3|samples'),
+    ((4, 512, 3, 4, 1, 1, 0, False), 'wgrad_mfma_kernel<2,1,2,2,1,1>|down1,k1'),
+    ((8, 512, 3, 4, 1, 1, 0, False), 'wgrad_mfma_kernel<2,1,2,2,1,1>|down1,k1'),
+    ((4, 512, 3, 8, 1, 1, 0, False), 'wgrad_mfma_kernel<2,1,2,2,1,1>|down1,k1'),
+    ((8, 512, 3, 8, 1, 1, 0, False), 'wgrad_mfma_kernel<2,1,2,2,1,1>|down1,k1'),
+    ((4, 512, 3, 16, 1, 1, 0, False), 'wgrad_mfma_kernel<2,1,2,2,1,1>|down1,k1'),
+    ((8, 512, 3, 16, 1, 1, 0, False), 'wgrad_mfma_kernel<2,1,2,2,1,1>|down1,k1'),
+    ((4, 512, 3, 32, 1, 1, 0, False), 'wgrad_mfma_kernel<2,1,2,2,1,1>|down1,k1'),
+    ((8, 512, 3, 32, 1, 1, 0, False), 'wgrad_mfma_kernel<2,1,2,2,1,1>|down1,k1'),
+    ((4, 512, 3, 64, 1, 1, 0, False), 'pw_wgrad_kernel<true>|thin_dy|down1,k1'),
+    ((8, 512, 3, 64, 1, 1, 0, False), 'pw_wgrad_kernel<true>|thin_dy|down1,k1'),
+    ((4, 512, 3, 64, 1, 1, 0, True), 'pw_wgrad_kernel<true>|thin_dy|down1,k1|samples'),
+    ((8, 512, 3, 64, 1, 1, 0, True), 'pw_wgrad_kernel<true>|thin_dy|down1,k1|samples'),
+    ((4, 256, 3, 128, 1, 1, 0, False), 'pw_wgrad_kernel<true>|thin_dy|down1,k1'),
+    ((8, 256, 3, 128, 1, 1, 0, False), 'pw_wgrad_kernel<true>|thin_dy|down1,k1'),
+    ((4, 256, 3, 128, 1, 1, 0, True), 'pw_wgrad_kernel<true>|thin_dy|down1,k1|samples'),
+    ((8, 256, 3, 128, 1, 1, 0, True), 'pw_wgrad_kernel<true>|thin_dy|down1,k1|samples'),
+    ((4, 128, 3, 256, 1, 1, 0, False), 'pw_wgrad_kernel<true>|thin_dy|down1,k1'),
+    ((8, 128, 3, 256, 1, 1, 0, False), 'pw_wgrad_kernel<true>|thin_dy|down1,k1'),
+    ((4, 128, 3, 256, 1, 1, 0, True), 'pw_wgrad_kernel<true>|thin_dy|down1,k1|samples'),
+    ((8, 128, 3, 256, 1, 1, 0, True), 'pw_wgrad_kernel<true>|thin_dy|down1,k1|samples'),
+    ((4, 64, 3, 512, 1, 1, 0, False), 'pw_wgrad_kernel<true>|thin_dy|down1,k1'),
+    ((8, 64, 3, 512, 1, 1, 0, False), 'pw_wgrad_kernel<true>|thin_dy|down1,k1'),
+    ((4, 64, 3, 512, 1, 1, 0, True), 'pw_wgrad_kernel<true>|thin_dy|down1,k1|samples'),
+    ((8, 64, 3, 512, 1, 1, 0, True), 'pw_wgrad_kernel<true>|thin_dy|down1,k1|samples'),
+    ((4, 32, 3, 1024, 1, 1, 0, False), 'pw_wgrad_kernel<true>|thin_dy|down1,k1'),
+    ((8, 32, 3, 1024, 1, 1, 0, False), 'pw_wgrad_kernel<true>|thin_dy|down1,k1'),
+    ((4, 32, 3, 1024, 1, 1, 0, True), 'pw_wgrad_kernel<true>|thin_dy|down1,k1|samples'),
+    ((8, 32, 3, 1024, 1, 1, 0, True), 'pw_wgrad_kernel<true>|thin_dy|down1,k1|samples'),
+    ((4, 3, 32, 1024, 1, 1, 0, False), 'pw_wgrad_kernel<true>|thin_x|down1,k1'),
+    ((8, 3, 32, 1024, 1, 1, 0, False), 'pw_wgrad_kernel<true>|thin_x|down1,k1'),
+]
+
+
+@pytest.mark.parametrize('shape,prefix', STEP_WGRAD_SHAPES)
+def test_step_wgrad_shapes_reach_their_kernels(shape, prefix):
+    name = _wprobe(*shape)
+    assert name.startswith(prefix), (shape, name)
+
+
+def test_wgrad_probe_plans_and_modes():
+    """The plan suffix carries what a kernel name alone does not: splits, tiles per split, the band count of the wave-specialised kernel, a direct write."""
+    assert _wprobe(4, 512, 512, 64, 3, 1, 1) == 'wgrad_bf16x3_ws2_kernel|down1,k3|plan:splits=4,tiles_per_split=64,bands=4'
+    assert _wprobe(8, 512, 512, 32, 3, 1, 1, samples=True) == 'wgrad_bf16x3_ws2_kernel|down1,k3|samples|plan:splits=8,tiles_per_split=16,bands=2'
+    assert _wprobe(1, 64, 64, 2, 1, 1, 0, w=8) == 'wgrad_bf16x3_kernel<2,2,1,2,1>|down1,k1|plan:splits=1,tiles_per_split=1,direct'
+    assert _wprobe(4, 512, 512, 64, 3, 1, 1, mode='bf16') == _wprobe(4, 512, 512, 64, 3, 1, 1)       # the plain-bf16 build of the same kernels
+    assert _wprobe(4, 512, 512, 64, 3, 1, 1, mode='f32').startswith('wgrad_mfma_kernel<2,2,1,1,1,3>|down1,k3|plan:splits=')
+    assert _wprobe(4, 512, 512, 8, 3, 1, 1, mode='f32') == _wprobe(4, 512, 512, 8, 3, 1, 1) == 'wgrad_f32_small_kernel<1,2>|down1,k3|plan:groups=1,direct'
+    with pytest.raises(RuntimeError):            # fp32 arithmetic has a per-sample form for the thin 1x1 shapes only
+        _wprobe(4, 512, 512, 64, 3, 1, 1, samples=True, mode='f32')
+
+
+def test_every_step_wgrad_variant_has_a_kernel_case():
+    """Every weight-gradient kernel the step launches is also compared with fp64 on its own, at kernel level (tests/test_ops_gpu.py)."""
+    import test_ops_gpu as ops
+    step = {_kernel(_wprobe(*shape)) for shape, _ in STEP_WGRAD_SHAPES}
+    cases = set()
+    for (b, K, N, h, w, k, down, pad, _), fast, _ in ops.WGRAD_VARIANT_CASES:
+        name = _kernel(_wprobe(b, K, N, h, k, down, pad, w=w))
+        assert name == _kernel(fast), 'the case list pins the name it reaches'
+        cases.add(name)
+    for b, K, N, h, w, k, down, pad, _, variant in ops.SAMPLE_WGRAD_CASES:
+        name = _kernel(_wprobe(b, K, N, h, k, down, pad, samples=True, w=w))
+        assert name == _kernel(variant)
+        cases.add(name)
+    assert step <= cases, sorted(step - cases)
+
+
+def test_every_step_conv_variant_has_a_kernel_case():
+    """... and so is every forward kernel of STEP_SHAPES by a case of BF16_CASES."""
+    import test_ops_gpu as ops
+    step = {_probe(*shape)[0] for shape, _, _ in STEP_SHAPES}
+    cases = set()
+    for b, K, N, h, w, k, up, down, pad in ops.BF16_CASES:
+        oh, ow = _out(h, k, up, down, pad), _out(w, k, up, down, pad)
+        cases.add(conv_variant(ConvGeom(k, k, up, down, pad, pad, oh, ow), N, b, K, 'bf16x3', (h, w)))
+    assert step <= cases, sorted(step - cases)

@@ -1254,16 +1254,19 @@ def test_from_rgb_backward_fused_vs_three_launches(mode):
 
 
 SAMPLE_WGRAD_CASES = [
-    # b, K, N, h, w, k, down, pad, pitched x
-    (3, 64, 64, 48, 80, 3, 1, 1, False),       # 64k x 64n tiles, stride 1
-    (2, 32, 48, 70, 66, 3, 1, 1, False),       # 32 x 32 tiles of six rows, ragged channel tile
-    (4, 64, 96, 40, 40, 1, 1, 0, False),       # 1 x 1 on the matrix kernels
-    (2, 64, 128, 65, 65, 3, 2, 0, False),      # stride 2, 64k x 64n, one output row per tile
-    (3, 32, 64, 129, 129, 3, 2, 0, True),      # stride 2, 32k x 64n; x row-pitched as the transposed convolution leaves it
-    (5, 64, 64, 6, 6, 3, 1, 1, False),         # fewer tiles per sample than the splits wanted
-    (2, 128, 3, 128, 128, 1, 1, 0, False),     # ToRGB class: thin 1 x 1 on the vector ALUs
-    (2, 3, 64, 128, 128, 1, 1, 0, False),      # FromRGB class
-    (2, 160, 160, 64, 64, 3, 1, 1, False),     # 57 / 29 splits of a < 256 K-element tensor: the reduce passes with four lane groups per element group
+    # b, K, N, h, w, k, down, pad, pitched x, the variant gc_conv2d_wgrad_samples_* must reach in the bf16 modes (wgrad_variant(..., samples=True))
+    (3, 64, 64, 48, 80, 3, 1, 1, False, 'wgrad_bf16x3_kernel<2,2,1,2,3>|down1,k3|samples'),       # 64k x 64n tiles, stride 1
+    (2, 32, 48, 70, 66, 3, 1, 1, False, 'wgrad_bf16x3_kernel<1,1,4,6,3>|down1,k3|samples'),       # 32 x 32 tiles of six rows, ragged channel tile
+    (4, 64, 96, 40, 40, 1, 1, 0, False, 'wgrad_bf16x3_kernel<2,2,1,2,1>|down1,k1|samples'),       # 1 x 1 on the matrix kernels
+    (2, 64, 128, 65, 65, 3, 2, 0, False, 'wgrad_bf16x3_s2_kernel<1,3,1,4>|down2,k3|samples'),     # stride 2, 32k x 128n, one output row per tile
+    (3, 32, 64, 129, 129, 3, 2, 0, True, 'wgrad_bf16x3_s2_kernel<2,3,1>|down2,k3|samples'),       # stride 2, 32k x 64n; x row-pitched as the transposed convolution leaves it
+    (5, 64, 64, 6, 6, 3, 1, 1, False, 'wgrad_bf16x3_kernel<2,2,1,2,3>|down1,k3|samples|plan:splits=15,tiles_per_split=1'),       # fewer tiles per sample than the splits wanted
+    (2, 128, 3, 128, 128, 1, 1, 0, False, 'pw_wgrad_kernel<true>|thin_dy|down1,k1|samples'),      # ToRGB class: thin 1 x 1 on the vector ALUs
+    (2, 3, 64, 128, 128, 1, 1, 0, False, 'pw_wgrad_kernel<true>|thin_x|down1,k1|samples'),        # FromRGB class
+    (2, 160, 160, 64, 64, 3, 1, 1, False, 'wgrad_bf16x3_kernel<2,2,1,2,3>|down1,k3|samples|plan:splits=58,tiles_per_split=3'),   # 58 / 43 splits of a < 256 K-element tensor: the reduce passes with four lane groups per element group
+    (3, 512, 512, 32, 96, 3, 1, 1, False, 'wgrad_bf16x3_ws2_kernel|down1,k3|samples|plan:splits=9,tiles_per_split=16,bands=2'),  # wave-specialised: three splits per sample, two strips each
+    (2, 64, 64, 65, 65, 3, 2, 0, False, 'wgrad_bf16x3_s2_kernel<1,3,2>|down2,k3|samples'),        # stride 2, 64k x 64n, one output row per tile
+    (2, 64, 128, 64, 64, 1, 2, 0, False, 'wgrad_bf16x3_s2_kernel<1,1,1,4>|down2,k1|samples'),     # stride-2 1 x 1 (D's skip convolutions), 32k x 128n
 ]
 
 
@@ -1275,10 +1278,13 @@ def test_wgrad_samples_kernels(case, mode):
     plane products the route replaces)."""
     from gan_control_amd.models.op._backend import ConvGeom
     hip, emu = _be()
-    b, K, N, h, w, k, down, pad, pitched = case
-    gen = torch.Generator().manual_seed(hash(case) & 0xFFFF)
+    b, K, N, h, w, k, down, pad, pitched, variant = case
+    gen = torch.Generator().manual_seed(hash(case[:9]) & 0xFFFF)
     oh, ow = (h + 2 * pad - k) // down + 1, (w + 2 * pad - k) // down + 1
     geom = ConvGeom(k, k, 1, down, pad, pad, oh, ow)
+    if mode != 'f32' or variant.startswith('pw_'):
+        from gan_control_amd.utils.profiling import wgrad_variant
+        assert wgrad_variant(geom, N, b, K, mode, (h, w), samples=True).startswith(variant), 'this shape is meant to reach ' + variant
     x = torch.randn(b, K, h, w, generator=gen).to(DEV)
     dy = torch.randn(b, N, oh, ow, generator=gen).to(DEV)
     si = (torch.randn(b, K, generator=gen) + 1.5).to(DEV)
@@ -1355,5 +1361,153 @@ def test_torgb_fork(mode):
     prev, hip.conv_mode = hip.conv_mode, mode
     try:
         oc.check_torgb_fork(DEV, size=128, batch=3, tol=2e-4, pl_tol=5e-3)      # 2.4e-5 measured on the 4 x 4 ToRGB (gx - gfork cancels there)
+    finally:
+        hip.conv_mode = prev
+
+
+WGRAD_VARIANT_CASES = [
+    # (b, K, N, h, w, k, down, pad, pitched x), the variant gc_conv2d_wgrad_bf16x3_f32 / _bf16_f32 must reach, the variant gc_conv2d_wgrad_f32 must reach
+    # (wgrad_variant(); names frozen from the built library.  Where the split plan is what the case is about, the name is pinned with its plan.)
+    # wgrad_bf16x3_ws2_kernel: 3 / 2 / 1 row bands; out_w = 19 tiles + 8, exactly 32, 40, 86 tiles, 85 tiles + 20; 1..3 channel blocks on K and on N; B = 1 and odd;
+    # strips that do not divide among the splits (60 / 29, 90 / 43, 258 / 122) and exactly two per split (58 / 29); every split of a B > 1 case walks several samples
+    ((1, 192, 192, 48, 616, 3, 1, 1, False), 'wgrad_bf16x3_ws2_kernel|down1,k3|plan:splits=29,tiles_per_split=17,bands=3', 'wgrad_mfma_kernel<2,2,1,1,1,3>|down1,k3|plan:splits=57,tiles_per_split=17'),
+    ((29, 192, 192, 32, 32, 3, 1, 1, False), 'wgrad_bf16x3_ws2_kernel|down1,k3|plan:splits=29,tiles_per_split=16,bands=2', 'wgrad_mfma_kernel<2,2,1,1,1,3>|down1,k3|plan:splits=55,tiles_per_split=17'),
+    ((15, 128, 192, 48, 40, 3, 1, 1, False), 'wgrad_bf16x3_ws2_kernel|down1,k3|plan:splits=43,tiles_per_split=17,bands=3', 'wgrad_mfma_kernel<2,2,1,1,1,3>|down1,k3|plan:splits=85,tiles_per_split=17'),
+    ((3, 64, 128, 16, 2752, 3, 1, 1, False), 'wgrad_bf16x3_ws2_kernel|down1,k3|plan:splits=122,tiles_per_split=17,bands=1', 'wgrad_mfma_kernel<2,2,1,1,1,3>|down1,k3|plan:splits=243,tiles_per_split=17'),
+    ((3, 128, 64, 16, 2740, 3, 1, 1, False), 'wgrad_bf16x3_ws2_kernel|down1,k3|plan:splits=122,tiles_per_split=17,bands=1', 'wgrad_mfma_kernel<2,2,1,1,1,3>|down1,k3|plan:splits=243,tiles_per_split=17'),
+    # ... and the other side of its boundary, same channels: out_h % 16 != 0, fewer than two strips per split -> the one-role kernel
+    ((15, 128, 192, 47, 40, 3, 1, 1, False), 'wgrad_bf16x3_kernel<2,2,1,2,3>|down1,k3', 'wgrad_mfma_kernel<2,2,1,1,1,3>|down1,k3'),
+    ((7, 128, 192, 48, 40, 3, 1, 1, False), 'wgrad_bf16x3_kernel<2,2,1,2,3>|down1,k3', 'wgrad_mfma_kernel<2,2,1,1,1,3>|down1,k3'),
+    # wgrad_bf16x3_s2_kernel<1,k,1,4> (32k x 128n: K >= 64, K % 32 == 0, N % 128 == 0): 33 -> 16 and 34 -> 16, out_w 16 and 34, dense and row-pitched x, B = 1 and 3
+    ((1, 64, 128, 33, 33, 3, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,3,1,4>|down2,k3', 'wgrad_mfma_kernel<2,2,1,1,2,3>|down2,k3'),
+    ((3, 96, 256, 34, 70, 3, 2, 0, True), 'wgrad_bf16x3_s2_kernel<1,3,1,4>|down2,k3', 'wgrad_mfma_kernel<2,2,1,1,2,3>|down2,k3'),
+    ((1, 96, 128, 33, 33, 1, 2, 0, True), 'wgrad_bf16x3_s2_kernel<1,1,1,4>|down2,k1', 'wgrad_mfma_kernel<2,2,1,1,2,1>|down2,k1'),
+    ((3, 64, 256, 34, 70, 1, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,1,1,4>|down2,k1', 'wgrad_mfma_kernel<2,2,1,1,2,1>|down2,k1'),
+    # <2,k,1> (32k x 64n tiles of two rows: K = 32 .. 63; 48 = a ragged 32-channel block; N = 192 stays on 64-wide tiles)
+    ((1, 32, 64, 33, 33, 3, 2, 0, True), 'wgrad_bf16x3_s2_kernel<2,3,1>|down2,k3', 'wgrad_mfma_kernel<1,2,2,2,2,3>|down2,k3'),
+    ((3, 48, 192, 34, 70, 3, 2, 0, False), 'wgrad_bf16x3_s2_kernel<2,3,1>|down2,k3', 'wgrad_mfma_kernel<2,2,1,1,2,3>|down2,k3'),
+    ((1, 48, 64, 33, 33, 1, 2, 0, False), 'wgrad_bf16x3_s2_kernel<2,1,1>|down2,k1', 'wgrad_mfma_kernel<2,2,1,1,2,1>|down2,k1'),
+    ((3, 32, 128, 34, 70, 1, 2, 0, True), 'wgrad_bf16x3_s2_kernel<2,1,1>|down2,k1', 'wgrad_mfma_kernel<1,2,2,2,2,1>|down2,k1'),
+    # <1,k,2> (64k x 64n, one row: K >= 64 and N % 128 != 0, or K % 32 != 0)
+    ((1, 64, 64, 33, 33, 3, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,3,2>|down2,k3', 'wgrad_mfma_kernel<2,2,1,1,2,3>|down2,k3'),
+    ((3, 96, 192, 34, 70, 3, 2, 0, True), 'wgrad_bf16x3_s2_kernel<1,3,2>|down2,k3', 'wgrad_mfma_kernel<2,2,1,1,2,3>|down2,k3'),
+    ((1, 96, 192, 33, 33, 1, 2, 0, True), 'wgrad_bf16x3_s2_kernel<1,1,2>|down2,k1', 'wgrad_mfma_kernel<2,2,1,1,2,1>|down2,k1'),
+    ((3, 64, 64, 34, 70, 1, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,1,2>|down2,k1', 'wgrad_mfma_kernel<2,2,1,1,2,1>|down2,k1'),
+    ((2, 80, 128, 33, 41, 3, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,3,2>|down2,k3', 'wgrad_mfma_kernel<2,2,1,1,2,3>|down2,k3'),
+    # ... two tiles per split with an odd tile count (the last split has one) over five samples
+    ((5, 64, 128, 131, 33, 3, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,3,1,4>|down2,k3|plan:splits=163,tiles_per_split=2', 'wgrad_mfma_kernel<2,2,1,1,2,3>|down2,k3|plan:splits=163,tiles_per_split=2'),
+    ((5, 64, 64, 211, 33, 3, 2, 0, True), 'wgrad_bf16x3_s2_kernel<1,3,2>|down2,k3|plan:splits=263,tiles_per_split=2', 'wgrad_mfma_kernel<2,2,1,1,2,3>|down2,k3|plan:splits=263,tiles_per_split=2'),
+    ((5, 32, 64, 419, 33, 3, 2, 0, False), 'wgrad_bf16x3_s2_kernel<2,3,1>|down2,k3|plan:splits=263,tiles_per_split=2', 'wgrad_mfma_kernel<1,2,2,2,2,3>|down2,k3|plan:splits=263,tiles_per_split=2'),
+    # wgrad_bf16x3_kernel<1,1,4,6,k> (32 x 32 channel tiles of six rows) and <2,2,1,2,k> (64 x 64, two rows): out_h below and off the row count, out_w 4 .. 31 and
+    # across a tile, ragged channel blocks (40, 70, 130), pad 0 and 1 for both tap counts, an odd tile count at two tiles per split
+    ((2, 40, 70, 4, 20, 3, 1, 1, False), 'wgrad_bf16x3_kernel<1,1,4,6,3>|down1,k3', 'wgrad_mfma_kernel<2,2,1,1,1,3>|down1,k3'),
+    ((1, 32, 130, 9, 31, 3, 1, 0, False), 'wgrad_bf16x3_kernel<1,1,4,6,3>|down1,k3', 'wgrad_mfma_kernel<1,2,2,2,1,3>|down1,k3'),
+    ((3, 70, 40, 13, 37, 1, 1, 0, False), 'wgrad_bf16x3_kernel<1,1,4,6,1>|down1,k1', 'wgrad_mfma_kernel<2,2,1,2,1,1>|down1,k1'),
+    ((2, 48, 32, 8, 6, 1, 1, 1, False), 'wgrad_bf16x3_kernel<1,1,4,6,1>|down1,k1', 'wgrad_mfma_kernel<2,1,2,2,1,1>|down1,k1'),
+    ((7, 40, 48, 113, 20, 3, 1, 1, False), 'wgrad_bf16x3_kernel<1,1,4,6,3>|down1,k3|plan:splits=67,tiles_per_split=2', 'wgrad_mfma_kernel<2,2,1,1,1,3>|down1,k3|plan:splits=396,tiles_per_split=2'),
+    ((2, 70, 130, 1, 20, 3, 1, 1, False), 'wgrad_bf16x3_kernel<2,2,1,2,3>|down1,k3', 'wgrad_mfma_kernel<2,2,1,1,1,3>|down1,k3'),
+    ((1, 130, 70, 9, 31, 3, 1, 0, False), 'wgrad_bf16x3_kernel<2,2,1,2,3>|down1,k3', 'wgrad_mfma_kernel<2,2,1,1,1,3>|down1,k3'),
+    ((3, 64, 70, 5, 37, 1, 1, 0, False), 'wgrad_bf16x3_kernel<2,2,1,2,1>|down1,k1', 'wgrad_mfma_kernel<2,2,1,2,1,1>|down1,k1'),
+    ((2, 130, 64, 7, 4, 1, 1, 1, False), 'wgrad_bf16x3_kernel<2,2,1,2,1>|down1,k1', 'wgrad_mfma_kernel<2,2,1,2,1,1>|down1,k1'),
+    ((5, 130, 130, 25, 20, 3, 1, 1, False), 'wgrad_bf16x3_kernel<2,2,1,2,3>|down1,k3|plan:splits=33,tiles_per_split=2', 'wgrad_mfma_kernel<2,2,1,1,1,3>|down1,k3|plan:splits=42,tiles_per_split=3'),
+    # one tile, one split: the kernel writes dw itself (no reduce pass)
+    ((1, 64, 64, 2, 8, 1, 1, 0, False), 'wgrad_bf16x3_kernel<2,2,1,2,1>|down1,k1|plan:splits=1,tiles_per_split=1,direct', 'wgrad_mfma_kernel<2,2,1,2,1,1>|down1,k1|plan:splits=1,tiles_per_split=1,direct'),
+    ((1, 32, 32, 6, 8, 1, 1, 0, False), 'wgrad_bf16x3_kernel<1,1,4,6,1>|down1,k1|plan:splits=1,tiles_per_split=1,direct', 'wgrad_mfma_kernel<1,1,4,4,1,1>|down1,k1|plan:splits=2,tiles_per_split=1'),
+    # wgrad_f32_small_kernel (3x3, planes <= 8 x 8, K and N >= 64, at most two LDS-sized sample groups) on both sides of each limit: 8 x 8 | 8 x 9 | 9 x 9, 17 -> 8 | 19 -> 9,
+    # 63 channels, B = 7 | 8 | 14 | 15 (one group, two, two, back on the pixel tiles), 17 -> 8 at B = 6 | 7; its chunk counts: padded plane <= 64, <= 128, above
+    ((2, 64, 64, 8, 8, 3, 1, 1, False), 'wgrad_f32_small_kernel<1,2>|down1,k3|plan:groups=1,direct', 'wgrad_f32_small_kernel<1,2>|down1,k3|plan:groups=1,direct'),
+    ((2, 64, 64, 8, 9, 3, 1, 1, False), 'wgrad_bf16x3_kernel<2,2,1,2,3>|down1,k3', 'wgrad_mfma_kernel<2,2,1,1,1,3>|down1,k3'),
+    ((2, 64, 64, 9, 9, 3, 1, 1, False), 'wgrad_bf16x3_kernel<2,2,1,2,3>|down1,k3', 'wgrad_mfma_kernel<2,2,1,1,1,3>|down1,k3'),
+    ((2, 63, 64, 8, 8, 3, 1, 1, False), 'wgrad_bf16x3_kernel<1,1,4,6,3>|down1,k3', 'wgrad_mfma_kernel<2,2,1,1,1,3>|down1,k3'),
+    ((7, 64, 64, 8, 8, 3, 1, 1, False), 'wgrad_f32_small_kernel<1,2>|down1,k3|plan:groups=1,direct', 'wgrad_f32_small_kernel<1,2>|down1,k3|plan:groups=1,direct'),
+    ((8, 64, 64, 8, 8, 3, 1, 1, False), 'wgrad_f32_small_kernel<1,2>|down1,k3|plan:groups=2,direct', 'wgrad_f32_small_kernel<1,2>|down1,k3|plan:groups=2,direct'),
+    ((14, 64, 64, 8, 8, 3, 1, 1, False), 'wgrad_f32_small_kernel<1,2>|down1,k3|plan:groups=2,direct', 'wgrad_f32_small_kernel<1,2>|down1,k3|plan:groups=2,direct'),
+    ((15, 64, 64, 8, 8, 3, 1, 1, False), 'wgrad_bf16x3_kernel<2,2,1,2,3>|down1,k3', 'wgrad_mfma_kernel<2,2,1,1,1,3>|down1,k3'),
+    ((2, 64, 80, 5, 3, 3, 1, 1, False), 'wgrad_f32_small_kernel<1,1>|down1,k3|plan:groups=1,direct', 'wgrad_f32_small_kernel<1,1>|down1,k3|plan:groups=1,direct'),
+    ((2, 64, 64, 17, 17, 3, 2, 0, False), 'wgrad_f32_small_kernel<2,5>|down2,k3|plan:groups=1,direct', 'wgrad_f32_small_kernel<2,5>|down2,k3|plan:groups=1,direct'),
+    ((2, 64, 64, 19, 19, 3, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,3,2>|down2,k3', 'wgrad_mfma_kernel<2,2,1,1,2,3>|down2,k3'),
+    ((6, 64, 64, 17, 17, 3, 2, 0, False), 'wgrad_f32_small_kernel<2,5>|down2,k3|plan:groups=2,direct', 'wgrad_f32_small_kernel<2,5>|down2,k3|plan:groups=2,direct'),
+    ((7, 64, 64, 17, 17, 3, 2, 0, False), 'wgrad_bf16x3_s2_kernel<1,3,2>|down2,k3', 'wgrad_mfma_kernel<2,2,1,1,2,3>|down2,k3'),
+    ((1, 64, 128, 3, 9, 3, 2, 0, False), 'wgrad_f32_small_kernel<2,1>|down2,k3|plan:groups=1,direct', 'wgrad_f32_small_kernel<2,1>|down2,k3|plan:groups=1,direct'),
+    ((3, 72, 64, 11, 9, 3, 2, 0, False), 'wgrad_f32_small_kernel<2,2>|down2,k3|plan:groups=1,direct', 'wgrad_f32_small_kernel<2,2>|down2,k3|plan:groups=1,direct'),
+    # what the split-bf16 kernels do not take runs on wgrad_mfma_kernel in every mode: out_w < 4, K or N < 32, pad 2, stride 2 with padding; and its four tile
+    # configurations (64k x 64n, 32k x 64n, 64k x 32n, 32k x 32n) at both strides and tap counts
+    ((2, 64, 64, 8, 3, 1, 1, 0, False), 'wgrad_mfma_kernel<2,2,1,2,1,1>|down1,k1', 'wgrad_mfma_kernel<2,2,1,2,1,1>|down1,k1'),
+    ((2, 48, 64, 5, 3, 3, 1, 1, False), 'wgrad_mfma_kernel<2,2,1,1,1,3>|down1,k3', 'wgrad_mfma_kernel<2,2,1,1,1,3>|down1,k3'),
+    ((2, 64, 64, 12, 12, 3, 1, 2, False), 'wgrad_mfma_kernel<2,2,1,1,1,3>|down1,k3', 'wgrad_mfma_kernel<2,2,1,1,1,3>|down1,k3'),
+    ((3, 64, 64, 13, 13, 3, 2, 1, False), 'wgrad_mfma_kernel<2,2,1,1,2,3>|down2,k3', 'wgrad_mfma_kernel<2,2,1,1,2,3>|down2,k3'),
+    ((2, 64, 64, 13, 13, 1, 2, 1, False), 'wgrad_mfma_kernel<2,2,1,1,2,1>|down2,k1', 'wgrad_mfma_kernel<2,2,1,1,2,1>|down2,k1'),
+    ((2, 16, 64, 12, 13, 3, 1, 1, False), 'wgrad_mfma_kernel<1,2,2,2,1,3>|down1,k3', 'wgrad_mfma_kernel<1,2,2,2,1,3>|down1,k3'),
+    ((1, 64, 24, 11, 12, 3, 1, 1, False), 'wgrad_mfma_kernel<2,1,2,2,1,3>|down1,k3', 'wgrad_mfma_kernel<2,1,2,2,1,3>|down1,k3'),
+    ((3, 24, 24, 12, 9, 3, 1, 1, False), 'wgrad_mfma_kernel<1,1,4,4,1,3>|down1,k3', 'wgrad_mfma_kernel<1,1,4,4,1,3>|down1,k3'),
+    ((2, 16, 64, 12, 13, 1, 1, 0, False), 'wgrad_mfma_kernel<1,2,2,2,1,1>|down1,k1', 'wgrad_mfma_kernel<1,2,2,2,1,1>|down1,k1'),
+    ((1, 64, 24, 11, 12, 1, 1, 0, False), 'wgrad_mfma_kernel<2,1,2,2,1,1>|down1,k1', 'wgrad_mfma_kernel<2,1,2,2,1,1>|down1,k1'),
+    ((3, 24, 24, 12, 9, 1, 1, 0, False), 'wgrad_mfma_kernel<1,1,4,4,1,1>|down1,k1', 'wgrad_mfma_kernel<1,1,4,4,1,1>|down1,k1'),
+    ((2, 32, 32, 13, 15, 3, 2, 0, False), 'wgrad_mfma_kernel<1,1,4,4,2,3>|down2,k3', 'wgrad_mfma_kernel<1,1,4,4,2,3>|down2,k3'),
+    ((1, 16, 64, 13, 14, 3, 2, 0, False), 'wgrad_mfma_kernel<1,2,2,2,2,3>|down2,k3', 'wgrad_mfma_kernel<1,2,2,2,2,3>|down2,k3'),
+    ((3, 64, 24, 13, 13, 3, 2, 0, False), 'wgrad_mfma_kernel<2,1,2,2,2,3>|down2,k3', 'wgrad_mfma_kernel<2,1,2,2,2,3>|down2,k3'),
+    ((2, 24, 24, 13, 15, 1, 2, 0, False), 'wgrad_mfma_kernel<1,1,4,4,2,1>|down2,k1', 'wgrad_mfma_kernel<1,1,4,4,2,1>|down2,k1'),
+    ((1, 16, 64, 13, 14, 1, 2, 0, False), 'wgrad_mfma_kernel<1,2,2,2,2,1>|down2,k1', 'wgrad_mfma_kernel<1,2,2,2,2,1>|down2,k1'),
+    ((3, 64, 32, 13, 13, 1, 2, 0, False), 'wgrad_mfma_kernel<2,1,2,2,2,1>|down2,k1', 'wgrad_mfma_kernel<2,1,2,2,2,1>|down2,k1'),
+    # thin 1x1 (<= 4 channels on one side, >= 16384 pixels over the batch) on pw_wgrad_kernel: thin x and thin dy, 16-byte groups and ragged planes
+    ((2, 3, 40, 96, 96, 1, 1, 0, False), 'pw_wgrad_kernel<true>|thin_x|down1,k1', 'pw_wgrad_kernel<true>|thin_x|down1,k1'),
+    ((2, 40, 3, 95, 97, 1, 1, 0, False), 'pw_wgrad_kernel<false>|thin_dy|down1,k1', 'pw_wgrad_kernel<false>|thin_dy|down1,k1'),
+    ((2, 4, 64, 95, 97, 1, 1, 0, False), 'pw_wgrad_kernel<false>|thin_x|down1,k1', 'pw_wgrad_kernel<false>|thin_x|down1,k1'),
+    ((2, 70, 2, 96, 96, 1, 1, 0, False), 'pw_wgrad_kernel<true>|thin_dy|down1,k1', 'pw_wgrad_kernel<true>|thin_dy|down1,k1'),
+]
+_WGRAD_REFS = {}
+
+
+def _wgrad_operands(case):
+    b, K, N, h, w, k, down, pad, _ = case
+    gen = torch.Generator().manual_seed(hash(case) & 0xFFFF)
+    oh, ow = (h + 2 * pad - k) // down + 1, (w + 2 * pad - k) // down + 1
+    x = torch.randn(b, K, h, w, generator=gen)
+    dy = torch.randn(b, N, oh, ow, generator=gen)
+    si = torch.randn(b, K, generator=gen)
+    so = torch.rand(b, N, generator=gen) + 0.5
+    return x, dy, si, so, (oh, ow)
+
+
+def _wgrad_refs(case, x, dy, si, so, geom):
+    """EmulatedBackend.conv2d_wgrad in fp64 without and with the two scales: computed once per case, shared by the three arithmetic modes."""
+    if case not in _WGRAD_REFS:
+        emu = EmulatedBackend()
+        _WGRAD_REFS[case] = (emu.conv2d_wgrad(x.double(), dy.double(), None, None, geom), emu.conv2d_wgrad(x.double(), dy.double(), si.double(), so.double(), geom))
+    return _WGRAD_REFS[case]
+
+
+@pytest.mark.parametrize('mode', ['bf16x3', 'bf16', 'f32'])
+@pytest.mark.parametrize('case,fast,exact', WGRAD_VARIANT_CASES, ids=['%d-%dto%d-%dx%d-k%ds%dp%d%s' % (c[0][:8] + ('-pitched' if c[0][8] else '',)) for c in WGRAD_VARIANT_CASES])
+def test_conv2d_wgrad_variants(case, fast, exact, mode):
+    """Every kernel the weight-gradient dispatchers can pick (the split-bf16 launcher, the fp32 launcher, the small-plane kernel, the thin pointwise
+    kernel) against EmulatedBackend.conv2d_wgrad in fp64, on a shape that the dispatch probe confirms to reach it.  Bounds as everywhere in this file:
+    5e-5 split-bf16 (and the thin pointwise kernel), 2e-2 plain bf16 on the matrix kernels, 5e-6 exact fp32.  One repeat launch is bit-identical."""
+    from gan_control_amd import _lib
+    from gan_control_amd.models.op._backend import ConvGeom
+    from gan_control_amd.utils.profiling import wgrad_variant
+    hip, _ = _be()
+    b, K, N, h, w, k, down, pad, pitched = case
+    x, dy, si, so, (oh, ow) = _wgrad_operands(case)
+    geom = ConvGeom(k, k, 1, down, pad, pad, oh, ow)
+    name = wgrad_variant(geom, N, b, K, mode, (h, w))
+    print('wgrad variant:', mode, case, name)
+    assert name.startswith(exact if mode == 'f32' else fast), 'this shape is meant to reach ' + (exact if mode == 'f32' else fast)
+    tol = ({'bf16x3': 5e-5, 'bf16': 2e-2}[mode] if name.startswith('wgrad_bf16x3_') else 5e-5 if name.startswith('pw_wgrad_kernel') else 5e-6)
+    refs = _wgrad_refs(case, x, dy, si, so, geom)
+    prev, hip.conv_mode = hip.conv_mode, mode
+    try:
+        xd, dyd, sid, sod = x.to(DEV), dy.to(DEV), si.to(DEV), so.to(DEV)
+        if pitched:
+            xd = _pitched(xd, (w + 31) // 32 * 32)          # NaN in the padding columns: nothing may read them
+            assert _lib.row_pitch(xd)
+            if mode != 'f32':
+                assert _lib.load().gc_conv2d_in_pitch_ok(hip._desc(xd, N, geom), {'bf16x3': 1, 'bf16': 2}[mode], 1), 'this kernel is meant to read the pitched rows in place'
+        for ref, scales in ((refs[0], (None, None)), (refs[1], (sid, sod))):
+            out = hip.conv2d_wgrad(xd, dyd, scales[0], scales[1], geom)
+            err = rel_err(out, ref)
+            print('  scales' if scales[0] is not None else '  plain ', 'rel_err %.3g (bound %g)' % (err, tol))
+            assert err < tol, (name, scales[0] is not None, err)
+            assert torch.equal(out, hip.conv2d_wgrad(xd, dyd, scales[0], scales[1], geom)), 'the weight gradient must be run-to-run deterministic'
     finally:
         hip.conv_mode = prev
