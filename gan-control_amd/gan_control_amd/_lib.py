@@ -13,8 +13,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _DEFAULT = os.path.normpath(os.path.join(_HERE, '..', 'csrc', 'libgancontrol_hip.so'))
 
 ABI_VERSION = 2
+MODE_IDS = {'f32': 0, 'bf16x3': 1, 'bf16': 2}      # the `mode` argument of the per-arithmetic queries (gancontrol_hip.h)
 
-_c_float_p = ctypes.c_void_p
 _i32, _i64, _f32, _vp, _sz = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 
 

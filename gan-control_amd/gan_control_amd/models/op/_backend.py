@@ -5,18 +5,17 @@ implementation shipped is ``HipBackend`` (ctypes -> libgancontrol_hip.so).  Test
 emulation of the same interface to validate the autograd wiring on machines without a GPU;
 the product never does.
 """
-import contextlib
 import ctypes
 import math
 import os
-
-_PITCHED_OUTPUT = os.environ.get('GANCONTROL_PITCHED_OUTPUT', '1') != '0'      # dev knob: 0 = dense rows everywhere
 from collections import namedtuple
 
 import torch
 
 from ... import _lib
 from . import weight_cache
+
+_PITCHED_OUTPUT = os.environ.get('GANCONTROL_PITCHED_OUTPUT', '1') != '0'      # dev knob: 0 = dense rows everywhere
 
 # ctx.needs_input_grad of a custom Function is fixed at forward time: inside `autograd.grad(outputs, inputs=[...])` a backward
 # cannot see that only the listed inputs are wanted.  R1 (gradient w.r.t. the real images) and the path-length regulariser
@@ -133,6 +132,7 @@ class HipBackend:
     # 'f32': exact fp32 MFMA (the parity mode); 'bf16x3': split-bf16 MFMA, ~5e-6 relative error per layer;
     # 'bf16': one bf16 MFMA per product, fp32 accumulate and storage, ~3e-3 per layer (BASELINE config[1]; never the default)
     conv_mode = os.environ.get('GANCONTROL_CONV_PRECISION', 'f32')
+    _MODES = _lib.MODE_IDS
     _conv_plans = {}      # (shape, geometry, mode) -> the library's per-shape answers (see conv2d)
     _chunks = {}          # plane size -> gc_bias_act_bwd_chunks
 
@@ -142,10 +142,37 @@ class HipBackend:
             v = self._chunks[inner] = _lib.load().gc_bias_act_bwd_chunks(inner)
         return v
 
+    def _launch(self, dev, entry, *args, timed=None):
+        """The one way an entry that returns a status is called: `entry`, a symbol of the loaded library, runs with `dev` as the current device
+        (the kernels launch on the current device; the stream handle among `args` is the current stream of the tensors' device) and a
+        failure is reported under the name that was called.  timed: `self.timer and (lambda: (kind, kernel name, work))` at the nine timed
+        sites -- one attribute test, and nothing built, while no utils.profiling.KernelTimer is installed; with one, it brackets the call."""
+        fn = getattr(_lib.load(), entry)
+        t0 = None
+        if timed:
+            kind, name, work = timed()
+            t0 = self.timer.start(kind, name)
+        if dev.index is None or dev.index == torch.cuda.current_device():
+            rc = fn(*args)
+        else:
+            with torch.cuda.device(dev.index):
+                rc = fn(*args)
+        _lib.check(rc, entry)
+        if t0 is not None:
+            self.timer.stop(name, t0, work)
+
     @staticmethod
-    def _guard(dev):
-        idx = dev.index if dev.index is not None else torch.cuda.current_device()
-        return torch.cuda.device(idx) if idx != torch.cuda.current_device() else None
+    def _empty_rows(n, c, h, w, pitch, dev):
+        """An uninitialised [n, c, h, w] output; with a pitch, the view of rows `pitch` floats apart that _lib.row_pitch recognises."""
+        if pitch:
+            return torch.empty((n, c, h, pitch), dtype=torch.float32, device=dev)[..., :w]
+        return torch.empty((n, c, h, w), dtype=torch.float32, device=dev)
+
+    def _fir_out_pitch(self, out_w):
+        """Row pitch (floats) of a FIR output this wide, 0 = dense: the (H + 1)-wide output of the Blur in front of a stride-2 convolution (and
+        of the Blur adjoint in G) gets aligned rows for its 16-byte stores (4.4 -> 5.6 TB/s); the stride-2 kernels read the pitch
+        (gc_conv_desc.in_pitch)."""
+        return (out_w + 31) // 32 * 32 if (pitch_allowed() and out_w % 4 != 0 and out_w >= 129 and self.conv_mode != 'f32') else 0
 
     def _pitched_fir_ok(self, x, taps, up, down, out_h, out_w):
         return _lib.row_pitch(x) and self.upfirdn2d_act_supported(taps, up, down, out_h, out_w, x.shape[0] * x.shape[1])
@@ -157,41 +184,16 @@ class HipBackend:
             if self._pitched_fir_ok(x, taps, up, down, out_h, out_w):
                 return self.upfirdn2d_act(x, taps, pad_x0, pad_y0, out_h, out_w, flip, None, None, None, 1.0, 1.0, activate=False)
             x = x.contiguous()
-        elif (pitch_allowed() and out_w % 4 != 0 and out_w >= 129 and self.conv_mode != 'f32'
-              and self.upfirdn2d_act_supported(taps, up, down, out_h, out_w, x.shape[0] * x.shape[1])):
-            # the (H + 1)-wide output of the Blur in front of a stride-2 convolution (and of the Blur adjoint in G): aligned rows for its
-            # 16-byte stores (4.4 -> 5.6 TB/s); the stride-2 kernels read the pitch (gc_conv_desc.in_pitch)
-            return self.upfirdn2d_act(x, taps, pad_x0, pad_y0, out_h, out_w, flip, None, None, None, 1.0, 1.0, activate=False,
-                                      out_pitch=(out_w + 31) // 32 * 32)
+        elif (out_pitch := self._fir_out_pitch(out_w)) and self.upfirdn2d_act_supported(taps, up, down, out_h, out_w, x.shape[0] * x.shape[1]):
+            return self.upfirdn2d_act(x, taps, pad_x0, pad_y0, out_h, out_w, flip, None, None, None, 1.0, 1.0, activate=False, out_pitch=out_pitch)
         dev = _lib.require_cuda_f32(x, taps)
         n, c, h, w = x.shape
         y = torch.empty((n, c, out_h, out_w), dtype=x.dtype, device=dev)
         if y.numel() == 0:
             return y
-        lib = _lib.load()
-        g = self._guard(dev)
-        t0 = None
-        if self.timer:
-            name = 'upfirdn2d_generic_kernel'          # mirrors the dispatch of gc_upfirdn2d_f32
-            if tuple(taps.shape) == (4, 4) and n * c <= 65535:
-                if up == 1 and down == 1 and out_w >= 64 and out_h >= 16:
-                    name = 'fir44_tile_kernel'
-                elif up == 1 and down == 1 and (out_h + 3) * (out_w + 3) <= 1296:
-                    name = 'fir44_small_kernel'
-                elif (up, down) == (1, 2) and out_w >= 32 and out_h >= 8:
-                    name = 'fir44_down2_kernel'
-                elif (up, down) == (2, 1) and out_w >= 32 and out_h >= 8:
-                    name = 'fir44_up2_kernel'
-            t0 = self.timer.start('fir44', name)
-        if g: g.__enter__()
-        try:
-            rc = lib.gc_upfirdn2d_f32(_lib.ptr(x), _lib.ptr(taps), _lib.ptr(y), n * c, h, w, out_h, out_w,
-                                      taps.shape[0], taps.shape[1], up, up, down, down, pad_x0, pad_y0, int(flip), _lib.stream_of(x))
-        finally:
-            if g: g.__exit__(None, None, None)
-        _lib.check(rc, 'gc_upfirdn2d_f32')
-        if t0 is not None:
-            self.timer.stop(name, t0, 4.0 * (x.numel() + y.numel()))
+        self._launch(dev, 'gc_upfirdn2d_f32', _lib.ptr(x), _lib.ptr(taps), _lib.ptr(y), n * c, h, w, out_h, out_w,
+                     taps.shape[0], taps.shape[1], up, up, down, down, pad_x0, pad_y0, int(flip), _lib.stream_of(x),
+                     timed=self.timer and (lambda: ('fir44', self._fir_kernel_name(taps, up, down, out_h, out_w, n * c), 4.0 * (x.numel() + y.numel()))))
         return y
 
     @staticmethod
@@ -199,36 +201,37 @@ class HipBackend:
         """Shapes gc_upfirdn2d_act_f32 takes (the 4x4 tile kernel); everything else runs FIR and activation as two launches."""
         return tuple(taps.shape) == (4, 4) and up == 1 and down == 1 and out_w >= 64 and out_h >= 16 and planes <= 65535
 
+    @staticmethod
+    def _fir_kernel_name(taps, up, down, out_h, out_w, planes):
+        """The kernel gc_upfirdn2d_f32 runs for these extents (what the timer files the launch under): mirrors its dispatch."""
+        if tuple(taps.shape) == (4, 4) and planes <= 65535:
+            if up == 1 and down == 1 and out_w >= 64 and out_h >= 16:
+                return 'fir44_tile_kernel'
+            if up == 1 and down == 1 and (out_h + 3) * (out_w + 3) <= 1296:
+                return 'fir44_small_kernel'
+            if (up, down) == (1, 2) and out_w >= 32 and out_h >= 8:
+                return 'fir44_down2_kernel'
+            if (up, down) == (2, 1) and out_w >= 32 and out_h >= 8:
+                return 'fir44_up2_kernel'
+        return 'upfirdn2d_generic_kernel'
+
     def upfirdn2d_act(self, x, taps, pad_x0, pad_y0, out_h, out_w, flip, bias, noise, noise_w, slope, gain, activate=True, out_pitch=0):
         """gain * lrelu(FIR(x) + noise_w * noise + bias); see gc_upfirdn2d_act_f32 (gc_upfirdn2d_pitched_f32 for a row-pitched x)."""
         pitch = _lib.row_pitch(x)
         dev = _lib.require_cuda_f32(x, taps, bias, noise, noise_w, pitched=(x,))
         n, c, h, w = x.shape
-        if out_pitch:
-            y = torch.empty((n, c, out_h, out_pitch), dtype=x.dtype, device=dev)[..., :out_w]
-        else:
-            y = torch.empty((n, c, out_h, out_w), dtype=x.dtype, device=dev)
+        y = self._empty_rows(n, c, out_h, out_w, out_pitch, dev)
         if y.numel() == 0:
             return y
-        lib = _lib.load()
-        g = self._guard(dev)
-        t0 = self.timer.start('fir44', 'fir44_tile_kernel') if self.timer else None
-        if g: g.__enter__()
-        try:
-            if pitch or out_pitch or not activate:
-                rc = lib.gc_upfirdn2d_pitched_f32(_lib.ptr(x), _lib.ptr(taps), _lib.ptr(y), n, c, h, w, pitch or w, out_h, out_w, out_pitch or out_w,
-                                                  taps.shape[0], taps.shape[1],
-                                                  pad_x0, pad_y0, int(flip), int(bool(activate)), _lib.ptr(bias), _lib.ptr(noise), _lib.ptr(noise_w),
-                                                  float(slope), float(gain), _lib.stream_of(x))
-            else:
-                rc = lib.gc_upfirdn2d_act_f32(_lib.ptr(x), _lib.ptr(taps), _lib.ptr(y), n, c, h, w, out_h, out_w, taps.shape[0], taps.shape[1],
-                                              pad_x0, pad_y0, int(flip), _lib.ptr(bias), _lib.ptr(noise), _lib.ptr(noise_w), float(slope), float(gain),
-                                              _lib.stream_of(x))
-        finally:
-            if g: g.__exit__(None, None, None)
-        _lib.check(rc, 'gc_upfirdn2d_act_f32')
-        if t0 is not None:
-            self.timer.stop('fir44_tile_kernel', t0, 4.0 * (x.numel() + y.numel()))
+        timed = self.timer and (lambda: ('fir44', 'fir44_tile_kernel', 4.0 * (x.numel() + y.numel())))
+        if pitch or out_pitch or not activate:
+            self._launch(dev, 'gc_upfirdn2d_pitched_f32', _lib.ptr(x), _lib.ptr(taps), _lib.ptr(y), n, c, h, w, pitch or w, out_h, out_w, out_pitch or out_w,
+                         taps.shape[0], taps.shape[1], pad_x0, pad_y0, int(flip), int(bool(activate)), _lib.ptr(bias), _lib.ptr(noise), _lib.ptr(noise_w),
+                         float(slope), float(gain), _lib.stream_of(x), timed=timed)
+        else:
+            self._launch(dev, 'gc_upfirdn2d_act_f32', _lib.ptr(x), _lib.ptr(taps), _lib.ptr(y), n, c, h, w, out_h, out_w, taps.shape[0], taps.shape[1],
+                         pad_x0, pad_y0, int(flip), _lib.ptr(bias), _lib.ptr(noise), _lib.ptr(noise_w), float(slope), float(gain), _lib.stream_of(x),
+                         timed=timed)
         return y
 
     def upfirdn2d_mask(self, x, taps, pad_x0, pad_y0, out_h, out_w, flip, mask_ref, slope, gain):
@@ -242,13 +245,9 @@ class HipBackend:
         y = torch.empty((n, c, out_h, out_w), dtype=x.dtype, device=dev)
         if y.numel() == 0:
             return y
-        t0 = self.timer.start('fir44', 'fir44_tile_kernel') if self.timer else None
-        with (self._guard(dev) or contextlib.nullcontext()):
-            rc = _lib.load().gc_upfirdn2d_mask_f32(_lib.ptr(x), _lib.ptr(taps), _lib.ptr(y), n, c, h, w, pitch or w, out_h, out_w, taps.shape[0], taps.shape[1],
-                                                   pad_x0, pad_y0, int(flip), _lib.ptr(mask_ref), float(slope), float(gain), _lib.stream_of(x))
-        _lib.check(rc, 'gc_upfirdn2d_mask_f32')
-        if t0 is not None:
-            self.timer.stop('fir44_tile_kernel', t0, 4.0 * (x.numel() + 2 * y.numel()))
+        self._launch(dev, 'gc_upfirdn2d_mask_f32', _lib.ptr(x), _lib.ptr(taps), _lib.ptr(y), n, c, h, w, pitch or w, out_h, out_w, taps.shape[0], taps.shape[1],
+                     pad_x0, pad_y0, int(flip), _lib.ptr(mask_ref), float(slope), float(gain), _lib.stream_of(x),
+                     timed=self.timer and (lambda: ('fir44', 'fir44_tile_kernel', 4.0 * (x.numel() + 2 * y.numel()))))
         return y
 
     def upfirdn2d_actbwd(self, gy, y_ref, noise, taps, pad_x0, pad_y0, out_h, out_w, flip, slope, gain):
@@ -256,23 +255,15 @@ class HipBackend:
         noise-strength gradients in one pass over gy (gc_upfirdn2d_actbwd_f32).  gx comes back row-pitched when its width is odd."""
         dev = _lib.require_cuda_f32(gy, y_ref, noise, taps)
         n, c, h, w = gy.shape
-        lib = _lib.load()
-        tiles = lib.gc_upfirdn2d_actbwd_tiles(out_h, out_w)
-        out_pitch = (out_w + 31) // 32 * 32 if (pitch_allowed() and out_w % 4 != 0 and out_w >= 129 and self.conv_mode != 'f32') else 0
-        if out_pitch:
-            gx = torch.empty((n, c, out_h, out_pitch), dtype=gy.dtype, device=dev)[..., :out_w]
-        else:
-            gx = torch.empty((n, c, out_h, out_w), dtype=gy.dtype, device=dev)
+        tiles = _lib.load().gc_upfirdn2d_actbwd_tiles(out_h, out_w)
+        out_pitch = self._fir_out_pitch(out_w)
+        gx = self._empty_rows(n, c, out_h, out_w, out_pitch, dev)
         psum = torch.empty((n, c, tiles), dtype=gy.dtype, device=dev)
         pdot = torch.empty((n, c, tiles), dtype=gy.dtype, device=dev) if noise is not None else None
-        t0 = self.timer.start('fir44', 'fir44_tile_kernel') if self.timer else None
-        with (self._guard(dev) or contextlib.nullcontext()):
-            rc = lib.gc_upfirdn2d_actbwd_f32(_lib.ptr(gy), _lib.ptr(y_ref), _lib.ptr(noise), _lib.ptr(taps), _lib.ptr(gx), _lib.ptr(psum), _lib.ptr(pdot),
-                                             n, c, h, w, out_h, out_w, out_pitch, taps.shape[0], taps.shape[1], pad_x0, pad_y0, int(flip),
-                                             float(slope), float(gain), _lib.stream_of(gy))
-        _lib.check(rc, 'gc_upfirdn2d_actbwd_f32')
-        if t0 is not None:
-            self.timer.stop('fir44_tile_kernel', t0, 4.0 * (2 * gy.numel() + gx.numel()))
+        self._launch(dev, 'gc_upfirdn2d_actbwd_f32', _lib.ptr(gy), _lib.ptr(y_ref), _lib.ptr(noise), _lib.ptr(taps), _lib.ptr(gx), _lib.ptr(psum), _lib.ptr(pdot),
+                     n, c, h, w, out_h, out_w, out_pitch, taps.shape[0], taps.shape[1], pad_x0, pad_y0, int(flip),
+                     float(slope), float(gain), _lib.stream_of(gy),
+                     timed=self.timer and (lambda: ('fir44', 'fir44_tile_kernel', 4.0 * (2 * gy.numel() + gx.numel()))))
         return gx, psum, pdot
 
     # -- backward of a fused (<= 3 -> n) 1x1 convolution + bias + leaky-ReLU (D's FromRGB layer) without an activation-backward pass -------
@@ -286,17 +277,12 @@ class HipBackend:
         dev = _lib.require_cuda_f32(x, dy, y_ref)
         b, k, h, w = x.shape
         n = dy.shape[1]
-        lib = _lib.load()
-        nbytes = lib.gc_pw_act_wgrad_workspace(b, k, n, h * w)
+        nbytes = _lib.load().gc_pw_act_wgrad_workspace(b, k, n, h * w)
         ws = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=dev)
         out = torch.empty((k + 1, n), dtype=x.dtype, device=dev)
-        t0 = self.timer.start('wgrad') if self.timer else None
-        with (self._guard(dev) or contextlib.nullcontext()):
-            rc = lib.gc_pw_act_wgrad_f32(_lib.ptr(x), _lib.ptr(dy), _lib.ptr(y_ref), _lib.ptr(out), b, k, n, h * w, float(slope), float(gain),
-                                         _lib.ptr(ws), ws.numel() * 4, _lib.stream_of(x))
-        _lib.check(rc, 'gc_pw_act_wgrad_f32')
-        if t0 is not None:
-            self.timer.stop('wgrad_mfma_kernel(+reduce)', t0, 2.0 * b * k * n * h * w)
+        self._launch(dev, 'gc_pw_act_wgrad_f32', _lib.ptr(x), _lib.ptr(dy), _lib.ptr(y_ref), _lib.ptr(out), b, k, n, h * w, float(slope), float(gain),
+                     _lib.ptr(ws), ws.numel() * 4, _lib.stream_of(x),
+                     timed=self.timer and (lambda: ('wgrad', 'wgrad_mfma_kernel(+reduce)', 2.0 * b * k * n * h * w)))
         return out[:k].view(1, 1, k, n), out[k]
 
     def pw_act_dgrad(self, dy, y_ref, w_adj, slope, gain):
@@ -305,10 +291,8 @@ class HipBackend:
         b, n, h, w = dy.shape
         k = w_adj.shape[3]
         gx = torch.empty((b, k, h, w), dtype=dy.dtype, device=dev)
-        with (self._guard(dev) or contextlib.nullcontext()):
-            rc = _lib.load().gc_pw_act_dgrad_f32(_lib.ptr(dy), _lib.ptr(y_ref), _lib.ptr(w_adj), _lib.ptr(gx), b, n, k, h * w, float(slope), float(gain),
-                                                 _lib.stream_of(dy))
-        _lib.check(rc, 'gc_pw_act_dgrad_f32')
+        self._launch(dev, 'gc_pw_act_dgrad_f32', _lib.ptr(dy), _lib.ptr(y_ref), _lib.ptr(w_adj), _lib.ptr(gx), b, n, k, h * w, float(slope), float(gain),
+                     _lib.stream_of(dy))
         return gx
 
     def bias_act(self, x, bias, noise, noise_w, slope, gain):
@@ -319,18 +303,9 @@ class HipBackend:
             return y
         batch, ch = x.shape[0], x.shape[1]
         inner = x.numel() // (batch * ch)
-        lib = _lib.load()
-        g = self._guard(dev)
-        t0 = self.timer.start('bias_act') if self.timer else None
-        if g: g.__enter__()
-        try:
-            rc = lib.gc_bias_act_f32(_lib.ptr(x), _lib.ptr(bias), _lib.ptr(noise), _lib.ptr(noise_w), _lib.ptr(y),
-                                     batch, ch, inner, slope, gain, _lib.stream_of(x))
-        finally:
-            if g: g.__exit__(None, None, None)
-        _lib.check(rc, 'gc_bias_act_f32')
-        if t0 is not None:
-            self.timer.stop('bias_act_kernel', t0, 4.0 * (2 * x.numel() + ch + (noise.numel() if noise is not None else 0)))
+        self._launch(dev, 'gc_bias_act_f32', _lib.ptr(x), _lib.ptr(bias), _lib.ptr(noise), _lib.ptr(noise_w), _lib.ptr(y),
+                     batch, ch, inner, slope, gain, _lib.stream_of(x),
+                     timed=self.timer and (lambda: ('bias_act', 'bias_act_kernel', 4.0 * (2 * x.numel() + ch + (noise.numel() if noise is not None else 0)))))
         return y
 
     def bias_act_bwd(self, dy, y_ref, slope, gain):
@@ -338,14 +313,7 @@ class HipBackend:
         dx = torch.empty_like(dy)
         if dy.numel() == 0:
             return dx
-        lib = _lib.load()
-        g = self._guard(dev)
-        if g: g.__enter__()
-        try:
-            rc = lib.gc_bias_act_bwd_f32(_lib.ptr(dy), _lib.ptr(y_ref), _lib.ptr(dx), dy.numel(), slope, gain, _lib.stream_of(dy))
-        finally:
-            if g: g.__exit__(None, None, None)
-        _lib.check(rc, 'gc_bias_act_bwd_f32')
+        self._launch(dev, 'gc_bias_act_bwd_f32', _lib.ptr(dy), _lib.ptr(y_ref), _lib.ptr(dx), dy.numel(), slope, gain, _lib.stream_of(dy))
         return dx
 
     def bias_act_bwd_reduce(self, dy, y_ref, noise, slope, gain, self_dot=None):
@@ -357,7 +325,6 @@ class HipBackend:
         dev = _lib.require_cuda_f32(dy, y_ref, noise)
         batch, ch = dy.shape[0], dy.shape[1]
         inner = dy.numel() // (batch * ch)
-        lib = _lib.load()
         chunks = self._bwd_chunks(inner)
         dx = torch.empty_like(dy)
         psum = torch.empty((batch, ch, chunks), dtype=dy.dtype, device=dev)
@@ -367,15 +334,8 @@ class HipBackend:
             bias, noise_w = self_dot
             _lib.require_cuda_f32(dy, bias, noise_w)
             pself = torch.empty((batch, ch, chunks), dtype=dy.dtype, device=dev)
-        g = self._guard(dev)
-        if g: g.__enter__()
-        try:
-            rc = lib.gc_bias_act_bwd_reduce_self_f32(_lib.ptr(dy), _lib.ptr(y_ref), _lib.ptr(noise), _lib.ptr(bias), _lib.ptr(noise_w),
-                                                     _lib.ptr(dx), _lib.ptr(psum), _lib.ptr(pdot), _lib.ptr(pself),
-                                                     batch, ch, inner, slope, gain, _lib.stream_of(dy))
-        finally:
-            if g: g.__exit__(None, None, None)
-        _lib.check(rc, 'gc_bias_act_bwd_reduce_self_f32')
+        self._launch(dev, 'gc_bias_act_bwd_reduce_self_f32', _lib.ptr(dy), _lib.ptr(y_ref), _lib.ptr(noise), _lib.ptr(bias), _lib.ptr(noise_w),
+                     _lib.ptr(dx), _lib.ptr(psum), _lib.ptr(pdot), _lib.ptr(pself), batch, ch, inner, slope, gain, _lib.stream_of(dy))
         return dx, psum, pdot, pself
 
     def bias_act_bwd_reduce_adjoint(self, ggx, cs, cd, cw, y_ref, dx, noise, bias, noise_w, slope, gain, want_gyref):
@@ -383,7 +343,6 @@ class HipBackend:
         dev = _lib.require_cuda_f32(y_ref, ggx, cs, cd, cw, dx, noise, bias, noise_w)
         batch, ch = y_ref.shape[0], y_ref.shape[1]
         inner = y_ref.numel() // (batch * ch)
-        lib = _lib.load()
         chunks = self._bwd_chunks(inner)
         for t in (cs, cd, cw):
             if t is not None and tuple(t.shape) != (batch, ch, chunks):
@@ -392,15 +351,9 @@ class HipBackend:
         g_yref = torch.empty_like(y_ref) if (want_gyref and cw is not None) else None
         pgb = torch.empty((batch, ch, chunks), dtype=y_ref.dtype, device=dev) if cw is not None else None
         pgn = torch.empty((batch, ch, chunks), dtype=y_ref.dtype, device=dev) if (cw is not None and noise is not None) else None
-        g = self._guard(dev)
-        if g: g.__enter__()
-        try:
-            rc = lib.gc_bias_act_bwd_reduce_adjoint_f32(_lib.ptr(ggx), _lib.ptr(cs), _lib.ptr(cd), _lib.ptr(cw), _lib.ptr(y_ref), _lib.ptr(dx), _lib.ptr(noise),
-                                                        _lib.ptr(bias), _lib.ptr(noise_w), _lib.ptr(g_dy), _lib.ptr(g_yref), _lib.ptr(pgb), _lib.ptr(pgn),
-                                                        batch, ch, inner, slope, gain, _lib.stream_of(y_ref))
-        finally:
-            if g: g.__exit__(None, None, None)
-        _lib.check(rc, 'gc_bias_act_bwd_reduce_adjoint_f32')
+        self._launch(dev, 'gc_bias_act_bwd_reduce_adjoint_f32', _lib.ptr(ggx), _lib.ptr(cs), _lib.ptr(cd), _lib.ptr(cw), _lib.ptr(y_ref), _lib.ptr(dx),
+                     _lib.ptr(noise), _lib.ptr(bias), _lib.ptr(noise_w), _lib.ptr(g_dy), _lib.ptr(g_yref), _lib.ptr(pgb), _lib.ptr(pgn),
+                     batch, ch, inner, slope, gain, _lib.stream_of(y_ref))
         return g_dy, g_yref, pgb, pgn
 
     # -- f-2: forward pass of the FID feature network (inference) ---------------------------------------
@@ -415,9 +368,8 @@ class HipBackend:
             out = torch.empty((b, n, oh, ow), dtype=x.dtype, device=dev)
         if out.shape[0] != b or out.shape[2] != oh or out.shape[3] != ow or not out.is_contiguous():
             raise ValueError(f'conv2d_bn_relu: output {tuple(out.shape)} does not match [{b}, *, {oh}, {ow}]')
-        rc = _lib.load().gc_conv2d_bn_relu_f32(_lib.ptr(x.contiguous()), _lib.ptr(w.contiguous()), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(out),
-                                               b, k, n, h, wd, kh, kw, stride, pad_y, pad_x, int(bool(relu)), out.shape[1], chan_off, _lib.stream_of(x))
-        _lib.check(rc, 'gc_conv2d_bn_relu_f32')
+        self._launch(dev, 'gc_conv2d_bn_relu_f32', _lib.ptr(x), _lib.ptr(w), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(out),
+                     b, k, n, h, wd, kh, kw, stride, pad_y, pad_x, int(bool(relu)), out.shape[1], chan_off, _lib.stream_of(x))
         return out
 
     def pool2d(self, x, k, stride, pad, mode, out=None, chan_off=0):
@@ -427,24 +379,22 @@ class HipBackend:
         oh, ow = (h + 2 * pad - k) // stride + 1, (wd + 2 * pad - k) // stride + 1
         if out is None:
             out = torch.empty((b, c, oh, ow), dtype=x.dtype, device=dev)
-        rc = _lib.load().gc_pool2d_f32(_lib.ptr(x.contiguous()), _lib.ptr(out), b, c, h, wd, k, stride, pad, 0 if mode == 'max' else 1, out.shape[1], chan_off,
-                                       _lib.stream_of(x))
-        _lib.check(rc, 'gc_pool2d_f32')
+        self._launch(dev, 'gc_pool2d_f32', _lib.ptr(x), _lib.ptr(out), b, c, h, wd, k, stride, pad, 0 if mode == 'max' else 1, out.shape[1], chan_off,
+                     _lib.stream_of(x))
         return out
 
     def global_avgpool(self, x):
         dev = _lib.require_cuda_f32(x)
         b, c = x.shape[0], x.shape[1]
         out = torch.empty((b, c, 1, 1), dtype=x.dtype, device=dev)
-        _lib.check(_lib.load().gc_global_avgpool_f32(_lib.ptr(x.contiguous()), _lib.ptr(out), b * c, x.numel() // max(b * c, 1), _lib.stream_of(x)), 'gc_global_avgpool_f32')
+        self._launch(dev, 'gc_global_avgpool_f32', _lib.ptr(x), _lib.ptr(out), b * c, x.numel() // max(b * c, 1), _lib.stream_of(x))
         return out
 
     def resize_bilinear(self, x, out_h, out_w, mul=1.0, add=0.0):
         dev = _lib.require_cuda_f32(x)
         b, c, h, wd = x.shape
         out = torch.empty((b, c, out_h, out_w), dtype=x.dtype, device=dev)
-        _lib.check(_lib.load().gc_resize_bilinear_f32(_lib.ptr(x.contiguous()), _lib.ptr(out), b * c, h, wd, out_h, out_w, float(mul), float(add), _lib.stream_of(x)),
-                   'gc_resize_bilinear_f32')
+        self._launch(dev, 'gc_resize_bilinear_f32', _lib.ptr(x), _lib.ptr(out), b * c, h, wd, out_h, out_w, float(mul), float(add), _lib.stream_of(x))
         return out
 
     # -- the identity predictor of the embedding loss (losses/arc_face.py) ----------------------------------------------------------
@@ -456,9 +406,8 @@ class HipBackend:
         b, c = x.shape[0], x.shape[1]
         in_h, in_w = in_hw if adjoint else x.shape[2:]
         y = torch.empty((b, c, in_h, in_w) if adjoint else (b, c, out_h, out_w), dtype=x.dtype, device=dev)
-        rc = _lib.load().gc_crop_resize_ac_f32(_lib.ptr(x), _lib.ptr(y), b * c, in_h, in_w, top, left, crop_h, crop_w, out_h, out_w, int(bool(adjoint)),
-                                               _lib.stream_of(x))
-        _lib.check(rc, 'gc_crop_resize_ac_f32')
+        self._launch(dev, 'gc_crop_resize_ac_f32', _lib.ptr(x), _lib.ptr(y), b * c, in_h, in_w, top, left, crop_h, crop_w, out_h, out_w, int(bool(adjoint)),
+                     _lib.stream_of(x))
         return y
 
     def affine_prelu(self, x, scale, shift, alpha):
@@ -467,9 +416,8 @@ class HipBackend:
         dev = _lib.require_cuda_f32(x, scale, shift, alpha)
         y = torch.empty_like(x)
         b, c = x.shape[0], x.shape[1]
-        rc = _lib.load().gc_affine_prelu_f32(_lib.ptr(x), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(alpha), _lib.ptr(y), b, c, x.numel() // max(b * c, 1),
-                                             _lib.stream_of(x))
-        _lib.check(rc, 'gc_affine_prelu_f32')
+        self._launch(dev, 'gc_affine_prelu_f32', _lib.ptr(x), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(alpha), _lib.ptr(y), b, c, x.numel() // max(b * c, 1),
+                     _lib.stream_of(x))
         return y
 
     def affine_prelu_bwd(self, g, x, scale, shift, alpha, g2=None, g2_strided=False):
@@ -484,9 +432,8 @@ class HipBackend:
         if g2 is not None and tuple(g2.shape) != want:
             raise ValueError('affine_prelu_bwd: second gradient %s, expected %s' % (tuple(g2.shape), want))
         gx = torch.empty_like(g)
-        rc = _lib.load().gc_affine_prelu_bwd_f32(_lib.ptr(g), _lib.ptr(x), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(alpha), _lib.ptr(g2), mode, _lib.ptr(gx),
-                                                 b, c, h, w, _lib.stream_of(g))
-        _lib.check(rc, 'gc_affine_prelu_bwd_f32')
+        self._launch(dev, 'gc_affine_prelu_bwd_f32', _lib.ptr(g), _lib.ptr(x), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(alpha), _lib.ptr(g2), mode, _lib.ptr(gx),
+                     b, c, h, w, _lib.stream_of(g))
         return gx
 
     def plane_reduce(self, a, b=None, mul=1.0):
@@ -496,8 +443,7 @@ class HipBackend:
         dev = _lib.require_cuda_f32(a, b)
         out = torch.empty((a.shape[0], a.shape[1]), dtype=a.dtype, device=dev)
         planes = a.shape[0] * a.shape[1]
-        rc = _lib.load().gc_plane_reduce_f32(_lib.ptr(a), _lib.ptr(b), _lib.ptr(out), planes, a.numel() // max(planes, 1), float(mul), _lib.stream_of(a))
-        _lib.check(rc, 'gc_plane_reduce_f32')
+        self._launch(dev, 'gc_plane_reduce_f32', _lib.ptr(a), _lib.ptr(b), _lib.ptr(out), planes, a.numel() // max(planes, 1), float(mul), _lib.stream_of(a))
         return out
 
     def se_mlp(self, m, fc1, fc2):
@@ -507,8 +453,7 @@ class HipBackend:
         r = fc1.shape[0]
         z = torch.empty((b, r), dtype=m.dtype, device=dev)
         s = torch.empty((b, c), dtype=m.dtype, device=dev)
-        _lib.check(_lib.load().gc_se_mlp_f32(_lib.ptr(m.contiguous()), _lib.ptr(fc1.contiguous()), _lib.ptr(fc2.contiguous()), _lib.ptr(z), _lib.ptr(s), b, c, r,
-                                             _lib.stream_of(m)), 'gc_se_mlp_f32')
+        self._launch(dev, 'gc_se_mlp_f32', _lib.ptr(m), _lib.ptr(fc1), _lib.ptr(fc2), _lib.ptr(z), _lib.ptr(s), b, c, r, _lib.stream_of(m))
         return z, s
 
     def se_mlp_bwd(self, t, s, z, fc1, fc2, mul):
@@ -516,8 +461,8 @@ class HipBackend:
         dev = _lib.require_cuda_f32(t, s, z, fc1, fc2)
         b, c = t.shape
         gm = torch.empty((b, c), dtype=t.dtype, device=dev)
-        _lib.check(_lib.load().gc_se_mlp_bwd_f32(_lib.ptr(t.contiguous()), _lib.ptr(s.contiguous()), _lib.ptr(z.contiguous()), _lib.ptr(fc1.contiguous()),
-                                                 _lib.ptr(fc2.contiguous()), _lib.ptr(gm), b, c, fc1.shape[0], float(mul), _lib.stream_of(t)), 'gc_se_mlp_bwd_f32')
+        self._launch(dev, 'gc_se_mlp_bwd_f32', _lib.ptr(t), _lib.ptr(s), _lib.ptr(z), _lib.ptr(fc1), _lib.ptr(fc2), _lib.ptr(gm), b, c, fc1.shape[0], float(mul),
+                     _lib.stream_of(t))
         return gm
 
     def se_apply(self, r, s, shortcut=None, stride=1):
@@ -530,8 +475,7 @@ class HipBackend:
         sh, sw = (sc.shape[2], sc.shape[3]) if sc is not None else (0, 0)
         if sc is not None and (sc.shape[0] != b or sc.shape[1] != c):
             raise ValueError('se_apply: shortcut %s does not match %s' % (tuple(sc.shape), tuple(r.shape)))
-        rc = _lib.load().gc_se_apply_f32(_lib.ptr(r), _lib.ptr(s.contiguous()), _lib.ptr(sc), _lib.ptr(out), b * c, h, w, sh, sw, int(stride), _lib.stream_of(r))
-        _lib.check(rc, 'gc_se_apply_f32')
+        self._launch(dev, 'gc_se_apply_f32', _lib.ptr(r), _lib.ptr(s), _lib.ptr(sc), _lib.ptr(out), b * c, h, w, sh, sw, int(stride), _lib.stream_of(r))
         return out
 
     def small_gemm_ok(self, a, b):
@@ -547,14 +491,8 @@ class HipBackend:
             _lib.require_cuda_f32(bias)
         m, k, n = a.shape[0], a.shape[1], b.shape[1]
         out = torch.empty((m, n), dtype=torch.float32, device=dev)
-        g = self._guard(dev)
-        if g: g.__enter__()
-        try:
-            rc = _lib.load().gc_small_gemm_f32(_lib.ptr(a), a.stride(0), a.stride(1), _lib.ptr(b), b.stride(0), b.stride(1), _lib.ptr(bias),
-                                               float(beta), float(alpha), _lib.ptr(out), m, k, n, _lib.stream_of(a))
-        finally:
-            if g: g.__exit__(None, None, None)
-        _lib.check(rc, 'gc_small_gemm_f32')
+        self._launch(dev, 'gc_small_gemm_f32', _lib.ptr(a), a.stride(0), a.stride(1), _lib.ptr(b), b.stride(0), b.stride(1), _lib.ptr(bias),
+                     float(beta), float(alpha), _lib.ptr(out), m, k, n, _lib.stream_of(a))
         return out
 
     # -- the style path: every dense layer of one kind in ONE launch (op/style.py) ----------------------------------------
@@ -586,9 +524,7 @@ class HipBackend:
         for i in range(len(plan.specs)):
             g = table[i]
             g.x, g.y, g.w, g.bias = xp + xoff[i], yp + yoff[i], weights[i].data_ptr(), (biases[i].data_ptr() if biases[i] is not None else None)
-        with (self._guard(dev) or contextlib.nullcontext()):
-            rc = _lib.load().gc_grouped_linear_f32(table, len(plan.specs), batch, _lib.stream_of(x))
-        _lib.check(rc, 'gc_grouped_linear_f32')
+        self._launch(dev, 'gc_grouped_linear_f32', table, len(plan.specs), batch, _lib.stream_of(x))
         return y
 
     def grouped_linear_bwd_x(self, gy, batch, plan, weights):
@@ -600,9 +536,7 @@ class HipBackend:
         for i in range(len(plan.specs)):
             g = table[i]
             g.x, g.y, g.w, g.bias = xp + xoff[i], yp + yoff[i], weights[i].data_ptr(), None
-        with (self._guard(dev) or contextlib.nullcontext()):
-            rc = _lib.load().gc_grouped_linear_bwd_x_f32(table, len(plan.specs), batch, _lib.stream_of(gy))
-        _lib.check(rc, 'gc_grouped_linear_bwd_x_f32')
+        self._launch(dev, 'gc_grouped_linear_bwd_x_f32', table, len(plan.specs), batch, _lib.stream_of(gy))
         return gx
 
     def grouped_linear_bwd_w(self, gy, x, batch, plan, has_bias):
@@ -625,9 +559,7 @@ class HipBackend:
             g.x, g.y, g.w, g.bias = xp + xoff[i], yp + yoff[i], gw.data_ptr(), (gb.data_ptr() if gb is not None else None)
             gws.append(gw)
             gbs.append(gb)
-        with (self._guard(dev) or contextlib.nullcontext()):
-            rc = _lib.load().gc_grouped_linear_bwd_w_f32(table, len(specs), batch, _lib.stream_of(gy))
-        _lib.check(rc, 'gc_grouped_linear_bwd_w_f32')
+        self._launch(dev, 'gc_grouped_linear_bwd_w_f32', table, len(specs), batch, _lib.stream_of(gy))
         return gws, gbs
 
     def rows_sum_div(self, partial, den=None):
@@ -638,13 +570,7 @@ class HipBackend:
         out = torch.empty(lead, dtype=partial.dtype, device=dev)
         if rows == 0:
             return out
-        g = self._guard(dev)
-        if g: g.__enter__()
-        try:
-            rc = _lib.load().gc_rows_sum_div_f32(_lib.ptr(partial), _lib.ptr(den), _lib.ptr(out), rows, chunks, _lib.stream_of(partial))
-        finally:
-            if g: g.__exit__(None, None, None)
-        _lib.check(rc, 'gc_rows_sum_div_f32')
+        self._launch(dev, 'gc_rows_sum_div_f32', _lib.ptr(partial), _lib.ptr(den), _lib.ptr(out), rows, chunks, _lib.stream_of(partial))
         return out
 
     def plane_dot(self, a, b, den=None):
@@ -655,16 +581,9 @@ class HipBackend:
         dev = _lib.require_cuda_f32(a, b)
         batch, ch = a.shape[0], a.shape[1]
         inner = a.numel() // (batch * ch)
-        lib = _lib.load()
         chunks = self._bwd_chunks(inner)
         partial = torch.empty((batch, ch, chunks), dtype=a.dtype, device=dev)
-        g = self._guard(dev)
-        if g: g.__enter__()
-        try:
-            rc = lib.gc_plane_dot_f32(_lib.ptr(a), _lib.ptr(b), _lib.ptr(partial), batch * ch, inner, _lib.stream_of(a))
-        finally:
-            if g: g.__exit__(None, None, None)
-        _lib.check(rc, 'gc_plane_dot_f32')
+        self._launch(dev, 'gc_plane_dot_f32', _lib.ptr(a), _lib.ptr(b), _lib.ptr(partial), batch * ch, inner, _lib.stream_of(a))
         if den is None and chunks == 1:
             return partial.reshape(batch, ch)
         return self.rows_sum_div(partial, None if den is None else den.contiguous())
@@ -677,11 +596,10 @@ class HipBackend:
             b = b.contiguous()
         dev = _lib.require_cuda_f32(a, b, pitched=(a, b))
         batch, ch, rows, width = a.shape
-        lib = _lib.load()
-        chunks = lib.gc_plane_dot_pitched_chunks(rows)
+        chunks = _lib.load().gc_plane_dot_pitched_chunks(rows)
         partial = torch.empty((batch, ch, chunks), dtype=a.dtype, device=dev)
-        rc = lib.gc_plane_dot_pitched_f32(_lib.ptr(a), _lib.ptr(b), _lib.ptr(partial), batch * ch, rows, width, pa or width, pb or width, _lib.stream_of(a))
-        _lib.check(rc, 'gc_plane_dot_pitched_f32')
+        self._launch(dev, 'gc_plane_dot_pitched_f32', _lib.ptr(a), _lib.ptr(b), _lib.ptr(partial), batch * ch, rows, width, pa or width, pb or width,
+                     _lib.stream_of(a))
         return self.rows_sum_div(partial, None if den is None else den.contiguous())
 
     def weight_prep_batch(self, kind, items):
@@ -689,43 +607,39 @@ class HipBackend:
         items: 'layout' -> (src, taps, k, n, src_stride, dst_shape, dst_stride, flip, scale); 'pack' -> (w_t, conv-desc fields)."""
         if not items:
             return []
-        lib = _lib.load()
         dev = items[0][0].device
         outs = []
-        with (self._guard(dev) or contextlib.nullcontext()):
-            if kind == 'layout':
-                table = (_lib.WLayoutGroup * len(items))()
-                for g, (src, taps, k, n, src_stride, dst_shape, dst_stride, flip, scale) in zip(table, items):
-                    _lib.require_cuda_f32(src)
-                    dst = torch.empty(dst_shape, dtype=src.dtype, device=dev)
-                    g.src, g.dst, g.taps, g.k, g.n, g.flip_taps, g.scale = src.data_ptr(), dst.data_ptr(), taps, k, n, int(bool(flip)), float(scale)
-                    for i in range(3):
-                        g.src_stride[i], g.dst_stride[i] = src_stride[i], dst_stride[i]
-                    outs.append(dst)
-                _lib.check(lib.gc_weight_layout_grouped_f32(table, len(items), _lib.stream_of(items[0][0])), 'gc_weight_layout_grouped_f32')
-            elif kind == 'pack':
-                table = (_lib.WPackGroup * len(items))()
-                for g, (w_t, fields) in zip(table, items):
-                    _lib.require_cuda_f32(w_t)
-                    desc = _lib.ConvDesc(*fields)
-                    pbytes = lib.gc_conv2d_bf16x3_packed_bytes(desc)
-                    if pbytes == 0:      # a stale recipe (the shape has no packed form under this build): per-tensor make() decides
-                        raise _lib.UnsupportedError('weight_prep_batch: descriptor %r takes no packed weights' % (tuple(fields),))
-                    buf = torch.empty(pbytes // 4, dtype=torch.float32, device=dev)
-                    g.desc, g.w, g.packed, g.packed_bytes = desc, w_t.data_ptr(), buf.data_ptr(), pbytes
-                    outs.append(buf)
-                _lib.check(lib.gc_conv2d_pack_weights_bf16x3_grouped(table, len(items), _lib.stream_of(items[0][0])), 'gc_conv2d_pack_weights_bf16x3_grouped')
-            elif kind == 'wsq':
-                table = (_lib.WsqGroup * len(items))()
-                for g, (w,) in zip(table, items):
-                    _lib.require_cuda_f32(w)
-                    out = torch.empty(w.shape[:2], dtype=w.dtype, device=dev)
-                    g.w, g.g, g.out, g.rows, g.taps = w.data_ptr(), None, out.data_ptr(), w.shape[0] * w.shape[1], w.numel() // (w.shape[0] * w.shape[1])
-                    outs.append(out)
-                _lib.check(lib.gc_weight_sq_grouped_f32(table, len(items), _lib.stream_of(items[0][0])), 'gc_weight_sq_grouped_f32')
-            else:
-                # a kind this backend has no grouped entry for: the one answer weight_cache's refill takes as "do it per tensor" (ADVICE r5)
-                raise _lib.UnsupportedError('weight_prep_batch: no grouped form for %r' % (kind,))
+        if kind == 'layout':
+            entry, table = 'gc_weight_layout_grouped_f32', (_lib.WLayoutGroup * len(items))()
+            for g, (src, taps, k, n, src_stride, dst_shape, dst_stride, flip, scale) in zip(table, items):
+                _lib.require_cuda_f32(src)
+                dst = torch.empty(dst_shape, dtype=src.dtype, device=dev)
+                g.src, g.dst, g.taps, g.k, g.n, g.flip_taps, g.scale = src.data_ptr(), dst.data_ptr(), taps, k, n, int(bool(flip)), float(scale)
+                for i in range(3):
+                    g.src_stride[i], g.dst_stride[i] = src_stride[i], dst_stride[i]
+                outs.append(dst)
+        elif kind == 'pack':
+            entry, table = 'gc_conv2d_pack_weights_bf16x3_grouped', (_lib.WPackGroup * len(items))()
+            for g, (w_t, fields) in zip(table, items):
+                _lib.require_cuda_f32(w_t)
+                desc = _lib.ConvDesc(*fields)
+                pbytes = _lib.load().gc_conv2d_bf16x3_packed_bytes(desc)
+                if pbytes == 0:      # a stale recipe (the shape has no packed form under this build): per-tensor make() decides
+                    raise _lib.UnsupportedError('weight_prep_batch: descriptor %r takes no packed weights' % (tuple(fields),))
+                buf = torch.empty(pbytes // 4, dtype=torch.float32, device=dev)
+                g.desc, g.w, g.packed, g.packed_bytes = desc, w_t.data_ptr(), buf.data_ptr(), pbytes
+                outs.append(buf)
+        elif kind == 'wsq':
+            entry, table = 'gc_weight_sq_grouped_f32', (_lib.WsqGroup * len(items))()
+            for g, (w,) in zip(table, items):
+                _lib.require_cuda_f32(w)
+                out = torch.empty(w.shape[:2], dtype=w.dtype, device=dev)
+                g.w, g.g, g.out, g.rows, g.taps = w.data_ptr(), None, out.data_ptr(), w.shape[0] * w.shape[1], w.numel() // (w.shape[0] * w.shape[1])
+                outs.append(out)
+        else:
+            # a kind this backend has no grouped entry for: the one answer weight_cache's refill takes as "do it per tensor" (ADVICE r5)
+            raise _lib.UnsupportedError('weight_prep_batch: no grouped form for %r' % (kind,))
+        self._launch(dev, entry, table, len(items), _lib.stream_of(items[0][0]))
         return outs
 
     def weight_sq_bwd(self, weights, grads):
@@ -737,9 +651,7 @@ class HipBackend:
             out = torch.empty_like(w)
             t.w, t.g, t.out, t.rows, t.taps = w.data_ptr(), g.data_ptr(), out.data_ptr(), w.shape[0] * w.shape[1], w.numel() // (w.shape[0] * w.shape[1])
             outs.append(out)
-        with (self._guard(dev) or contextlib.nullcontext()):
-            rc = _lib.load().gc_weight_sq_bwd_grouped_f32(table, len(weights), _lib.stream_of(weights[0]))
-        _lib.check(rc, 'gc_weight_sq_bwd_grouped_f32')
+        self._launch(dev, 'gc_weight_sq_bwd_grouped_f32', table, len(weights), _lib.stream_of(weights[0]))
         return outs
 
     def weight_layout(self, src, taps, k, n, src_stride, dst_shape, dst_stride, flip, scale):
@@ -748,16 +660,9 @@ class HipBackend:
         dst = torch.empty(dst_shape, dtype=src.dtype, device=dev)
         if dst.numel() != taps * k * n or src.numel() != taps * k * n:
             raise RuntimeError('weight_layout: %d x %d x %d elements expected, got src %d / dst %d' % (taps, k, n, src.numel(), dst.numel()))
-        lib = _lib.load()
         i64x3 = ctypes.c_int64 * 3
-        g = self._guard(dev)
-        if g: g.__enter__()
-        try:
-            rc = lib.gc_weight_layout_f32(_lib.ptr(src), _lib.ptr(dst), taps, k, n, ctypes.byref(i64x3(*src_stride)), ctypes.byref(i64x3(*dst_stride)),
-                                          int(bool(flip)), float(scale), _lib.stream_of(src))
-        finally:
-            if g: g.__exit__(None, None, None)
-        _lib.check(rc, 'gc_weight_layout_f32')
+        self._launch(dev, 'gc_weight_layout_f32', _lib.ptr(src), _lib.ptr(dst), taps, k, n, ctypes.byref(i64x3(*src_stride)), ctypes.byref(i64x3(*dst_stride)),
+                     int(bool(flip)), float(scale), _lib.stream_of(src))
         return dst
 
     def channel_sum(self, x):
@@ -768,16 +673,9 @@ class HipBackend:
         if x.numel() == 0:
             return out.zero_()
         inner = x.numel() // (batch * ch)
-        lib = _lib.load()
-        nbytes = lib.gc_channel_sum_workspace(batch, ch, inner)
+        nbytes = _lib.load().gc_channel_sum_workspace(batch, ch, inner)
         ws = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=dev)
-        g = self._guard(dev)
-        if g: g.__enter__()
-        try:
-            rc = lib.gc_channel_sum_f32(_lib.ptr(x), _lib.ptr(out), batch, ch, inner, _lib.ptr(ws), ws.numel() * 4, _lib.stream_of(x))
-        finally:
-            if g: g.__exit__(None, None, None)
-        _lib.check(rc, 'gc_channel_sum_f32')
+        self._launch(dev, 'gc_channel_sum_f32', _lib.ptr(x), _lib.ptr(out), batch, ch, inner, _lib.ptr(ws), ws.numel() * 4, _lib.stream_of(x))
         return out
 
     def affine_warp(self, x, mat, in_h, in_w, out_h, out_w, adjoint):
@@ -792,14 +690,8 @@ class HipBackend:
         y = torch.empty((b, c) + ((in_h, in_w) if adjoint else (out_h, out_w)), dtype=x.dtype, device=dev)
         if y.numel() == 0:
             return y
-        lib = _lib.load()
-        g = self._guard(dev)
-        if g: g.__enter__()
-        try:
-            rc = lib.gc_affine_warp_bilinear_f32(_lib.ptr(x), _lib.ptr(mat), _lib.ptr(y), b, c, in_h, in_w, out_h, out_w, int(bool(adjoint)), _lib.stream_of(x))
-        finally:
-            if g: g.__exit__(None, None, None)
-        _lib.check(rc, 'gc_affine_warp_bilinear_f32')
+        self._launch(dev, 'gc_affine_warp_bilinear_f32', _lib.ptr(x), _lib.ptr(mat), _lib.ptr(y), b, c, in_h, in_w, out_h, out_w, int(bool(adjoint)),
+                     _lib.stream_of(x))
         return y
 
     def reflect_pad(self, x, pads, adjoint, in_hw):
@@ -809,14 +701,7 @@ class HipBackend:
         h, w = in_hw
         b, c = x.shape[0], x.shape[1]
         y = torch.empty((b, c, h, w) if adjoint else (b, c, h + top + bottom, w + left + right), dtype=x.dtype, device=dev)
-        lib = _lib.load()
-        g = self._guard(dev)
-        if g: g.__enter__()
-        try:
-            rc = lib.gc_reflect_pad_f32(_lib.ptr(x), _lib.ptr(y), b * c, h, w, left, right, top, bottom, int(bool(adjoint)), _lib.stream_of(x))
-        finally:
-            if g: g.__exit__(None, None, None)
-        _lib.check(rc, 'gc_reflect_pad_f32')
+        self._launch(dev, 'gc_reflect_pad_f32', _lib.ptr(x), _lib.ptr(y), b * c, h, w, left, right, top, bottom, int(bool(adjoint)), _lib.stream_of(x))
         return y
 
     @staticmethod
@@ -829,10 +714,13 @@ class HipBackend:
 
         epilogue = (bias [N] | None, noise [B,1,oh,ow] | None, noise_w [1] | None, slope, gain, activate[, residual [B,N,oh,ow] | None]) or None.
         """
+        mode = self.conv_mode
+        if mode not in self._MODES:
+            raise RuntimeError('GANCONTROL_CONV_PRECISION must be f32, bf16x3 or bf16, got %r' % mode)
         lib = _lib.load()
         n_out = w_t.shape[3]
         desc = self._desc(x, n_out, geom)
-        mode_id = {'f32': 0, 'bf16x3': 1, 'bf16': 2}.get(self.conv_mode, 0)
+        mode_id = self._MODES[mode]
         # the library's per-shape answers (packed-weight bytes, split-K bytes, whether / how the output is row-pitched) do not change
         # between calls: each is asked once per (shape, mode, pitches) -- up to four ctypes round trips less per convolution on the host
         pkey = (x.shape[0], x.shape[1], n_out, x.shape[2], x.shape[3], geom, mode_id)
@@ -845,7 +733,7 @@ class HipBackend:
             return v
         in_pitch = _lib.row_pitch(x)
         if in_pitch:          # the pitched output of a Blur: the split-bf16 stride-2 kernel reads it in place
-            if geom.down == 2 and lib.gc_conv2d_in_pitch_ok(desc, {'f32': 0, 'bf16x3': 1, 'bf16': 2}.get(self.conv_mode, 0), 0):
+            if geom.down == 2 and lib.gc_conv2d_in_pitch_ok(desc, mode_id, 0):
                 desc.in_pitch = in_pitch
             else:
                 x = x.contiguous()
@@ -857,9 +745,7 @@ class HipBackend:
         pitch = ask('out_pitch', lib.gc_conv2d_out_pitch, mode_id) if (geom.up == 2 and x.shape[0] > 0 and pitch_allowed()) else 0
         if pitch:
             desc.out_pitch = pitch
-            y = torch.empty((x.shape[0], n_out, geom.out_h, pitch), dtype=x.dtype, device=dev)[..., :geom.out_w]
-        else:
-            y = torch.empty((x.shape[0], n_out, geom.out_h, geom.out_w), dtype=x.dtype, device=dev)
+        y = self._empty_rows(x.shape[0], n_out, geom.out_h, geom.out_w, pitch, dev)
         if y.numel() == 0:
             return y
         ep = None
@@ -875,14 +761,16 @@ class HipBackend:
                 raise RuntimeError('conv2d epilogue: noise has %d elements, expected %d' % (noise.numel(), x.shape[0] * geom.out_h * geom.out_w))
             ep = ctypes.byref(_lib.ConvEpilogue(_lib.ptr(bias), _lib.ptr(noise), _lib.ptr(noise_w), float(slope), float(gain), int(bool(activate)), _lib.ptr(residual)))
         ws = packed = None
-        if self.conv_mode in ('bf16x3', 'bf16'):
+        if mode == 'f32':
+            nbytes = ask('f32ws', lib.gc_conv2d_f32_workspace)          # K slices of a small-plane launch (planes <= 16 px wide), else 0
+            ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev) if nbytes else None
+        else:
             pbytes = ask('packed', lib.gc_conv2d_bf16x3_packed_bytes)
             if pbytes:
                 # hi / lo split of the weights: once per (weight, optimiser step) when w_t derives from a parameter (weight_cache.py)
                 def pack():
                     buf = torch.empty(pbytes // 4, dtype=torch.float32, device=dev)
-                    with (self._guard(dev) or contextlib.nullcontext()):
-                        _lib.check(lib.gc_conv2d_pack_weights_bf16x3(desc, _lib.ptr(w_t), _lib.ptr(buf), pbytes, _lib.stream_of(w_t)), 'gc_conv2d_pack_weights_bf16x3')
+                    self._launch(dev, 'gc_conv2d_pack_weights_bf16x3', desc, _lib.ptr(w_t), _lib.ptr(buf), pbytes, _lib.stream_of(w_t))
                     return buf
                 packed = weight_cache.derive(w_t, ('pack_bf16x3',), pack, recipe=lambda: ('pack', tuple(getattr(desc, f) for f, _ in _lib.ConvDesc._fields_)))
                 sbytes = ask('splitk', lib.gc_conv2d_bf16x3_splitk_bytes)          # K slices of a small-plane launch
@@ -890,45 +778,35 @@ class HipBackend:
             else:
                 nbytes = lib.gc_conv2d_bf16x3_workspace(desc)
                 ws = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=dev)
-        elif self.conv_mode == 'f32':
-            nbytes = ask('f32ws', lib.gc_conv2d_f32_workspace)          # K slices of a small-plane launch (planes <= 16 px wide), else 0
-            ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev) if nbytes else None
-        else:
-            raise RuntimeError('GANCONTROL_CONV_PRECISION must be f32, bf16x3 or bf16, got %r' % self.conv_mode)
-        g = self._guard(dev)
-        t0 = None
-        if self.timer:
-            from ...utils.profiling import conv_variant, conv_flops
-            tname = conv_variant(geom, n_out, x.shape[0], x.shape[1], self.conv_mode, in_hw=(x.shape[2], x.shape[3]))
-            t0 = self.timer.start('conv', tname)
-        if g: g.__enter__()
-        try:
-            if self.conv_mode == 'f32':
-                rc = lib.gc_conv2d_fused_f32_ws(desc, _lib.ptr(x), _lib.ptr(w_t), _lib.ptr(in_scale), _lib.ptr(out_scale), ep, _lib.ptr(y),
-                                                _lib.ptr(ws), ws.numel() * 4 if ws is not None else 0, _lib.stream_of(x))
-            elif packed is not None:
-                fn = lib.gc_conv2d_fused_bf16_packed_f32 if self.conv_mode == 'bf16' else lib.gc_conv2d_fused_bf16x3_packed_f32
-                rc = fn(desc, _lib.ptr(x), _lib.ptr(w_t), _lib.ptr(packed), packed.numel() * 4, _lib.ptr(in_scale),
-                                                           _lib.ptr(out_scale), ep, _lib.ptr(y), _lib.ptr(ws), ws.numel() * 4 if ws is not None else 0, _lib.stream_of(x))
-            else:
-                rc = lib.gc_conv2d_fused_bf16x3_packed_f32(desc, _lib.ptr(x), _lib.ptr(w_t), None, 0, _lib.ptr(in_scale), _lib.ptr(out_scale), ep, _lib.ptr(y),
-                                                           _lib.ptr(ws), ws.numel() * 4, _lib.stream_of(x))
-        finally:
-            if g: g.__exit__(None, None, None)
-        _lib.check(rc, 'gc_conv2d_fused_f32')
-        if t0 is not None:
-            self.timer.stop(tname, t0, conv_flops(x.shape[0], x.shape[1], n_out, x.shape[2], x.shape[3], geom))
+        timed = self.timer and (lambda: self._conv_timed(x, n_out, geom, mode))
+        tail = (ep, _lib.ptr(y), _lib.ptr(ws), ws.numel() * 4 if ws is not None else 0, _lib.stream_of(x))
+        if mode == 'f32':
+            self._launch(dev, 'gc_conv2d_fused_f32_ws', desc, _lib.ptr(x), _lib.ptr(w_t), _lib.ptr(in_scale), _lib.ptr(out_scale), *tail, timed=timed)
+        else:     # without packed weights (no packed form for this shape) the bf16x3 entry splits them itself, in either arithmetic
+            entry = 'gc_conv2d_fused_bf16_packed_f32' if (mode == 'bf16' and packed is not None) else 'gc_conv2d_fused_bf16x3_packed_f32'
+            self._launch(dev, entry, desc, _lib.ptr(x), _lib.ptr(w_t), _lib.ptr(packed), packed.numel() * 4 if packed is not None else 0,
+                         _lib.ptr(in_scale), _lib.ptr(out_scale), *tail, timed=timed)
         return y
 
     def conv2d_wgrad(self, x, dy, in_scale, out_scale, geom):
         in_pitch = _lib.row_pitch(x)
         if in_pitch or _lib.row_pitch(dy):
-            n_out_ = dy.shape[1]
-            ok = in_pitch and geom.down == 2 and _lib.load().gc_conv2d_in_pitch_ok(self._desc(x, n_out_, geom), {'f32': 0, 'bf16x3': 1, 'bf16': 2}.get(self.conv_mode, 0), 1)
+            ok = in_pitch and geom.down == 2 and _lib.load().gc_conv2d_in_pitch_ok(self._desc(x, dy.shape[1], geom), self._MODES.get(self.conv_mode, 0), 1)
             if not ok:
                 x, in_pitch = x.contiguous(), 0
             dy = dy.contiguous()
         return self._conv2d_wgrad(x, dy, in_scale, out_scale, geom, in_pitch)
+
+    @staticmethod
+    def _conv_timed(x, n_out, geom, mode):
+        from ...utils.profiling import conv_variant, conv_flops
+        return ('conv', conv_variant(geom, n_out, x.shape[0], x.shape[1], mode, in_hw=(x.shape[2], x.shape[3])),
+                conv_flops(x.shape[0], x.shape[1], n_out, x.shape[2], x.shape[3], geom))
+
+    @staticmethod
+    def _wgrad_timed(x, n_out, geom):
+        from ...utils.profiling import conv_flops
+        return 'wgrad', 'wgrad_mfma_kernel(+reduce)', conv_flops(x.shape[0], x.shape[1], n_out, x.shape[2], x.shape[3], geom)
 
     def _conv2d_wgrad(self, x, dy, in_scale, out_scale, geom, in_pitch=0):
         """x [B,K,H,W], dy [B,N,out_h,out_w] -> dw [kh,kw,K,N]; see gc_conv2d_wgrad_f32."""
@@ -944,22 +822,10 @@ class HipBackend:
         if nbytes is None:
             nbytes = self._conv_plans[wkey] = (lib.gc_conv2d_wgrad_bf16x3_workspace if fast else lib.gc_conv2d_wgrad_workspace)(desc)
         ws = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=dev)
-        g = self._guard(dev)
-        t0 = self.timer.start('wgrad') if self.timer else None
-        if g: g.__enter__()
-        try:
-            fn = (lib.gc_conv2d_wgrad_bf16_f32 if self.conv_mode == 'bf16' else lib.gc_conv2d_wgrad_bf16x3_f32) if fast else lib.gc_conv2d_wgrad_f32
-            rc = fn(desc, _lib.ptr(x), _lib.ptr(dy), _lib.ptr(in_scale), _lib.ptr(out_scale), _lib.ptr(dw),
-                    _lib.ptr(ws), ws.numel() * 4, _lib.stream_of(x))
-        finally:
-            if g: g.__exit__(None, None, None)
-        _lib.check(rc, 'gc_conv2d_wgrad_f32')
-        if t0 is not None:
-            from ...utils.profiling import conv_flops
-            self.timer.stop('wgrad_mfma_kernel(+reduce)', t0, conv_flops(x.shape[0], x.shape[1], n_out, x.shape[2], x.shape[3], geom))
+        entry = {'bf16x3': 'gc_conv2d_wgrad_bf16x3_f32', 'bf16': 'gc_conv2d_wgrad_bf16_f32'}.get(self.conv_mode, 'gc_conv2d_wgrad_f32')
+        self._launch(dev, entry, desc, _lib.ptr(x), _lib.ptr(dy), _lib.ptr(in_scale), _lib.ptr(out_scale), _lib.ptr(dw),
+                     _lib.ptr(ws), ws.numel() * 4, _lib.stream_of(x), timed=self.timer and (lambda: self._wgrad_timed(x, n_out, geom)))
         return dw
-
-    _MODES = {'f32': 0, 'bf16x3': 1, 'bf16': 2}
 
     def conv2d_wgrad_samples_bytes(self, x, dy, geom):
         """Scratch bytes of conv2d_wgrad_samples for these operands in the current arithmetic, 0 = this shape has no per-sample form."""
@@ -986,21 +852,10 @@ class HipBackend:
         dws = torch.empty((x.shape[0], geom.kh, geom.kw, x.shape[1], n_out), dtype=x.dtype, device=dev)
         desc = self._desc(x, n_out, geom)
         desc.in_pitch = in_pitch
-        lib = _lib.load()
         ws = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=dev)
-        fn = {'bf16x3': lib.gc_conv2d_wgrad_samples_bf16x3_f32, 'bf16': lib.gc_conv2d_wgrad_samples_bf16_f32}.get(self.conv_mode, lib.gc_conv2d_wgrad_samples_f32)
-        g = self._guard(dev)
-        t0 = self.timer.start('wgrad') if self.timer else None
-        if g: g.__enter__()
-        try:
-            rc = fn(desc, _lib.ptr(x), _lib.ptr(dy), _lib.ptr(in_scale), _lib.ptr(out_scale), _lib.ptr(dw), _lib.ptr(dws),
-                    _lib.ptr(ws), ws.numel() * 4, _lib.stream_of(x))
-        finally:
-            if g: g.__exit__(None, None, None)
-        _lib.check(rc, 'gc_conv2d_wgrad_samples_f32')
-        if t0 is not None:
-            from ...utils.profiling import conv_flops
-            self.timer.stop('wgrad_mfma_kernel(+reduce)', t0, conv_flops(x.shape[0], x.shape[1], n_out, x.shape[2], x.shape[3], geom))
+        entry = {'bf16x3': 'gc_conv2d_wgrad_samples_bf16x3_f32', 'bf16': 'gc_conv2d_wgrad_samples_bf16_f32'}.get(self.conv_mode, 'gc_conv2d_wgrad_samples_f32')
+        self._launch(dev, entry, desc, _lib.ptr(x), _lib.ptr(dy), _lib.ptr(in_scale), _lib.ptr(out_scale), _lib.ptr(dw), _lib.ptr(dws),
+                     _lib.ptr(ws), ws.numel() * 4, _lib.stream_of(x), timed=self.timer and (lambda: self._wgrad_timed(x, n_out, geom)))
         return dw, dws
 
     def wgrad_samples_contract(self, dws, w, scale_a, scale_c, want_a=True, want_c=True):
@@ -1012,16 +867,9 @@ class HipBackend:
             raise ValueError(f'wgrad_samples_contract: shapes {tuple(dws.shape)} / {tuple(w.shape)}')
         g_a = torch.empty((b, a), dtype=dws.dtype, device=dev) if want_a else None
         g_c = torch.empty((b, c), dtype=dws.dtype, device=dev) if want_c else None
-        lib = _lib.load()
         ws = torch.empty(max(b * a * c, 4), dtype=torch.float32, device=dev) if want_c else None
-        g = self._guard(dev)
-        if g: g.__enter__()
-        try:
-            rc = lib.gc_wgrad_samples_contract_f32(_lib.ptr(dws), _lib.ptr(w), _lib.ptr(scale_a), _lib.ptr(scale_c), _lib.ptr(g_a), _lib.ptr(g_c),
-                                                   b, taps, a, c, _lib.ptr(ws), ws.numel() * 4 if ws is not None else 0, _lib.stream_of(dws))
-        finally:
-            if g: g.__exit__(None, None, None)
-        _lib.check(rc, 'gc_wgrad_samples_contract_f32')
+        self._launch(dev, 'gc_wgrad_samples_contract_f32', _lib.ptr(dws), _lib.ptr(w), _lib.ptr(scale_a), _lib.ptr(scale_c), _lib.ptr(g_a), _lib.ptr(g_c),
+                     b, taps, a, c, _lib.ptr(ws), ws.numel() * 4 if ws is not None else 0, _lib.stream_of(dws))
         return g_a, g_c
 
 

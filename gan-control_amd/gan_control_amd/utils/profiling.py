@@ -12,9 +12,9 @@ import collections
 
 import torch
 
+from .._lib import MODE_IDS as _MODES
 
 _VARIANTS = {}
-_MODES = {'f32': 0, 'bf16x3': 1, 'bf16': 2}
 
 
 def conv_variant(geom, n_out, batch=1, k_in=64, mode='f32', in_hw=None):

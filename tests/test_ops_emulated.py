@@ -264,3 +264,31 @@ def test_weight_cache_recipes_do_not_outlive_their_tensor():
         assert wc._recipes_of(live) == {('wsq',): ('wsq',)} and wc._recipes[id(live)][0]() is live
     finally:
         wc._recipes.pop(id(live), None)
+
+
+def test_hip_backend_mirrors_the_emulated_interface():
+    """Every primitive of the emulation (conftest.EmulatedBackend) exists on HipBackend under the same leading parameter names; the HIP side
+    may only add trailing keywords (upfirdn2d_act's activate / out_pitch) and methods the emulation lacks (ArcFace, small GEMM)."""
+    import inspect
+    from conftest import EmulatedBackend
+    from gan_control_amd.models.op._backend import HipBackend
+    extra = {}
+    for name, fn in inspect.getmembers(EmulatedBackend, inspect.isfunction):
+        if name.startswith('_'):
+            continue
+        want = list(inspect.signature(fn).parameters)
+        have = list(inspect.signature(getattr(HipBackend, name)).parameters)
+        assert have[:len(want)] == want, name
+        if have[len(want):]:
+            extra[name] = have[len(want):]
+    assert extra == {'upfirdn2d_act': ['activate', 'out_pitch']}
+    only_hip = {n for n, _ in inspect.getmembers(HipBackend, inspect.isfunction) if not n.startswith('_')} - set(dir(EmulatedBackend))
+    assert only_hip == {'crop_resize_ac', 'affine_prelu', 'affine_prelu_bwd', 'plane_reduce', 'se_mlp', 'se_mlp_bwd', 'se_apply', 'small_gemm_ok', 'small_gemm'}
+
+
+def test_one_mode_id_map():
+    from gan_control_amd import _lib
+    from gan_control_amd.models.op._backend import HipBackend
+    from gan_control_amd.utils import profiling
+    assert profiling._MODES is _lib.MODE_IDS and HipBackend._MODES is _lib.MODE_IDS
+    assert _lib.MODE_IDS == {'f32': 0, 'bf16x3': 1, 'bf16': 2}
