@@ -5,6 +5,11 @@ what it returns, never reads an output or a workspace before writing it, and sta
 ``gc_*_bytes`` / ``gc_conv2d_out_pitch`` queries grant.  Every case runs three times on the same inputs -- plain, under NaN poison, under a large
 finite poison -- and must give the same bits each time, with every guard word intact.
 
+The READ side of the same contract (``test_entry_on_hostile_inputs``): every case runs again with each INPUT placed by ``guarded_alloc.hostile`` --
+NaN, 1e30 or zeros in front of it, behind it and in the padding columns of a row-pitched one, the guards of every backend allocation holding the
+same word -- and once with every dense input 4 bytes off its 512-byte boundary.  The outputs must be finite and the plain run's bits each time: a
+result that depends on a byte outside the logical elements of an input differs between the fills or is NaN.
+
 CPU part (no marker): the harness's own self-test, the completeness of the case table against the entries named in ``op/_backend.py`` and the coverage
 of the kernel variants by the no-launch dispatch probe.  GPU part (``-m gpu``): the case table and one whole training iteration.
 """
@@ -160,6 +165,11 @@ def wgrad_sources(mode):
 # involved, the call sequence of test_wgrad_samples_kernels -- ended in "an illegal memory access was encountered" on the MI355X when it ran in this
 # file's process (after 176 other cases; x and dy are each exactly 9 x 2 MiB there).  The cause has not been found by reading wgrad_bf16x3_ws2_kernel,
 # wgrad_reduce_samples_kernel and the two contract kernels, so the case stays out, in both arithmetics that share the code, until it is.
+# Ruled out since: a read past x or dy through the scalar offset of the "+16" loads (wgrad_bf16x3.hip:420, :445).  Both tensors end on the last byte
+# of a 2 MiB-granular allocator segment there, and for channel K - 1, the last input row, the last column tile and unit 4 the lane offset is
+# xbytes - 4 with 16 in the scalar operand: a load that would touch xbytes + 12 if the range check looked at the lane offset alone.  It does not:
+# on gfx950 the scalar offset is part of the check (tools/micro/buf_soffset.hip; SCALAR_OFFSET_RULE_CASE below), the load returns zeros and reaches
+# no memory.  The same holds for every load and store of the convolution kernels that carries a channel or a half unit in the scalar operand.
 NOT_RUN = {'wgrad_bf16x3_ws2_kernel|down1,k3|samples': ('bf16x3', 'bf16')}
 
 LARGE_WGRAD = (3, 64, 64, 96, 96, 3, 1, 1, False)          # tests/test_ops_gpu.py::test_conv2d_large_wgrad_splits
@@ -792,6 +802,41 @@ def _():
     return build, run
 
 
+# ---- inputs 4 bytes off a 512-byte boundary: what may differ from the plain run --------------------------------------------------------------------
+# By default a case gives the plain run's bits for a base that is only 4-byte aligned: the launchers that branch on (pointer & 15) choose between
+# 16-byte and 4-byte ACCESSES of the same elements in the same order (bias_act.hip, pointwise.hip -- pw_wgrad_kernel<VEC> sums the same four-pixel
+# groups either way --, arcface.hip, upfirdn2d.hip, conv.hip:117).  The reduce passes of conv.hip:1194/1206 branch on the alignment of a workspace
+# and an output, which the backend allocates itself: no input placement reaches them.
+# SHIFT_REORDERS: cases in which an unaligned input changes the summation ORDER; the named outputs are held to _TOL[case.mode or 'f32'] against the
+# plain run, the others to its bits.  {case name: (the line that branches, the outputs it reorders)}.
+SHIFT_REORDERS = {
+    # channel_sum_stage1 sums a chunk as four interleaved partial sums per lane over 16-byte loads when the plane's base is 16-byte aligned and its
+    # bounds are multiples of four, and as one sum per lane over single floats otherwise; of the three tensors of the case only the 128 x 128 planes
+    # qualify for the first form (33 x 31 and 10-element planes take the second at any alignment)
+    'channel_sum': ('bias_act.hip:293', (2,)),
+}
+# SHIFT_REFUSES: cases whose entry refuses an unaligned base; {case name: the error text it must raise}.  The grouped-linear kernels read x and w
+# with 16-byte loads at row strides that are multiples of four floats, so the launcher checks both bases (style.hip:240); op/_backend.py passes
+# the pointers on as they come.
+SHIFT_REFUSES = {'grouped_linear-%s' % name: 'x and w must be 16-byte aligned'
+                 for tag in ('ragged', '40-groups') for name in ('fwd-' + tag, 'bwd_x-' + tag, 'bwd_x-%s-unread-block' % tag, 'bwd_w-' + tag)}
+SHIFT_EXCEPTION_CAP = 10          # per cent of CASES, both lists together; more than that is a finding to report, not a list to widen
+
+# ---- the range check of a raw buffer access on gfx950: is the scalar offset part of it? -------------------------------------------------------------
+# No forward kernel MULTIPLIES a value it loaded through a nonzero scalar offset from beyond its descriptor: conv_bf16x3_kernel and
+# convt_fused_bf16x3_kernel clamp the channel to K - 1 (conv_bf16x3.hip:227, convt_bf16x3.hip:143; the weights and s_si are zero past K), the
+# wave-specialised kernels take K % 16 == 0 only (ws_eligible, s2ws_eligible), and what a 16-byte load fetches past a row end is selected away
+# (`i < inrow`).  The weight-gradient kernels select too (unit8, x_store, y_store).  So no NaN behind an input can tell the two rules apart, for any
+# of the load sites.  The STORES of conv_bf16x3_kernel do (conv_bf16x3.hip:386): an output channel goes into the scalar offset, `ocs * oplane`, and the
+# lane offset is the pixel plus `4 * hi` planes.  In the case below N = 20 and the channel tile is 32, so every pixel is stored for the channels 20 ..
+# 31 as well, with a lane offset below N * oplane.  Were the scalar offset outside the range check, those stores would pass it and land
+# (ocs - 20) planes behind the sample: for the last sample in the trailing guard of y (12 planes of 35 x 33 floats = 55 440 bytes, inside the 64 KiB
+# guard), where check() reports them.  With the scalar offset inside the check they are dropped, which is what the kernel's comments assume.
+# Measured on the MI355X: the guards of this case stay intact, and tools/micro/buf_soffset.hip, which asks the hardware directly inside one owned
+# allocation, prints zeros for every load whose lane + scalar offset reaches num_records and drops the store: the scalar offset IS part of the check.
+SCALAR_OFFSET_RULE_CASE = 'conv2d-bf16x3-conv_bf16x3_kernel<1,4,1,1>|up1,down2,k3-2x40x20x71x67x3x1x2x0'
+
+
 # ====================================================================================================================================================
 # CPU tests
 # ====================================================================================================================================================
@@ -889,6 +934,136 @@ def test_harness_proxy_forwards_and_restores():
     assert g.entries == ['gc_one', 'gc_two']
 
 
+def _hostile_forms():
+    """A dense tensor, a row-pitched one and a transposed view, with values that no fill can be mistaken for."""
+    gen = _gen('hostile', 1)
+    return {'dense': torch.randn(3, 5, 7, generator=gen), 'pitched': _pitched(torch.randn(2, 3, 4, 5, generator=gen), 32), 't': torch.randn(6, 9, generator=gen).t()}
+
+
+def _words_around(h):
+    """(the word in front of the view's first byte, the first word behind its last) of a hostile() tensor, as int32."""
+    rec = h._hostile
+    span = ga._storage_elems(tuple(h.shape), tuple(h.stride())) * h.element_size()
+    assert rec.first % 4 == 0
+    return int(rec.backing[rec.first // 4 - 1]), int(rec.backing[(rec.first + span + 3) // 4])
+
+
+def test_hostile_keeps_the_tensor_and_fills_everything_around_it():
+    for form, t in _hostile_forms().items():
+        for fill, word in ga.FILLS.items():
+            for shift in (0, 4):
+                h = ga.hostile(t, fill, shift)
+                assert h.shape == t.shape and h.stride() == t.stride() and h.dtype == t.dtype and h.data_ptr() % 512 == shift, (form, fill, shift)
+                assert torch.equal(h, t) and h.storage_offset() * 4 == h._hostile.first and ga.hostile_changes(h, t) is None
+                assert _words_around(h) == (word, word), (form, fill, shift)
+                rec = h._hostile
+                span = ga._storage_elems(tuple(t.shape), tuple(t.stride())) * 4
+                assert rec.first >= max(64 << 10, span) and rec.backing.numel() * 4 - (rec.first + span) >= max(64 << 10, span)          # both guards
+                # every word of the buffer that is no logical element holds the fill: guards, pitch padding, the gaps of the transposed view's span
+                mask = torch.ones_like(rec.backing, dtype=torch.bool)
+                idx = torch.as_strided(torch.arange(rec.backing.numel()), tuple(t.shape), tuple(t.stride()), rec.first // 4)
+                mask[idx.reshape(-1)] = False
+                assert int(mask.sum()) == rec.backing.numel() - t.numel() and bool((rec.backing[mask] == word).all()), (form, fill, shift)
+    pitched = ga.hostile(_hostile_forms()['pitched'], 'nan')
+    assert _lib.row_pitch(pitched) == 32          # still what the library reads in place
+    padding = torch.as_strided(pitched, (2, 3, 4, 27), pitched.stride(), pitched.storage_offset() + 5)
+    assert bool(torch.isnan(padding[:, :, :3]).all())
+    with pytest.raises(ValueError):
+        ga.hostile(torch.zeros(3), 'canary')
+    with pytest.raises(ValueError):
+        ga.hostile(torch.zeros(3), 'nan', 2)
+    # a store anywhere in the buffer is reported: behind, in front, into a logical element
+    t = torch.zeros(3, 5)
+    h = ga.hostile(t, 'big', 4)
+    raw = torch.as_strided(h, (17,), (1,), h.storage_offset() - 1)
+    raw[16] = 1.0
+    assert ga.hostile_changes(h, t) == {'offset': 60, 'words': 1}
+    raw[0] = 1.0
+    h[0, 2] = 5.0
+    assert ga.hostile_changes(h, t) == {'offset': -4, 'words': 3}
+    raw[0], raw[16] = 1e30, 1e30          # ... and a store into a logical element alone
+    assert ga.hostile_changes(h, t) == {'offset': 8, 'words': 1}
+    with pytest.raises(ValueError):
+        ga.hostile(torch.zeros(3, dtype=torch.int64), 'nan')
+
+
+def _sum_one_past(h):
+    """A wrong "kernel": sums the elements of a dense input and the one behind it."""
+    return torch.as_strided(h, (h.numel() + 1,), (1,), h.storage_offset()).sum()
+
+
+def _sum_one_in_front(h):
+    return torch.as_strided(h, (h.numel() + 1,), (1,), h.storage_offset() - 1).sum()
+
+
+def _row_sums_over_the_pitch(h):
+    """Another: sums each row of a row-pitched input over one column too many."""
+    b, c, rows, w = h.shape
+    return torch.as_strided(h, (b, c, rows, w + 1), h.stride(), h.storage_offset()).sum(-1)
+
+
+def test_hostile_fills_expose_reads_outside_an_input():
+    forms = _hostile_forms()
+    for wrong, t in ((_sum_one_past, forms['dense']), (_sum_one_in_front, forms['dense']), (_row_sums_over_the_pitch, forms['pitched'])):
+        for shift in (0, 4) if t.is_contiguous() else (0,):
+            got = {fill: wrong(ga.hostile(t, fill, shift)) for fill in ga.FILLS}
+            assert bool(torch.isnan(got['nan']).all()), wrong.__name__
+            assert bool(torch.isfinite(got['big']).all()) and not torch.equal(got['big'], got['zero']), wrong.__name__
+    # correct "kernels" -- a sum over the logical elements, a weighted sum over a transposed view -- give the same bits under all three fills
+    m = torch.randn(9, 6, generator=_gen('hostile', 2))
+    for right, t in ((lambda h: h.sum((0, 1)), forms['dense']), (lambda h: h.sum(-1), forms['pitched']), (lambda h: (h * m).sum(1), forms['t'])):
+        want = right(t).view(torch.int32)
+        for fill in ga.FILLS:
+            for shift in (0, 4):
+                assert torch.equal(right(ga.hostile(t, fill, shift)).view(torch.int32), want), (fill, shift)
+
+
+def test_harness_canary_word_is_the_neighbourhood_and_still_reports_a_store():
+    for name, word in ga.POISONS.items():
+        with ga.guarded(_Module, name, canary=word) as g:
+            t = _Module.torch.zeros((3, 5), dtype=torch.float32, device='cpu')
+            rec = g.allocations[0]
+            assert g.check() == [] and bool((rec.front == word).all()) and bool((rec.back == word).all())
+            # what a kernel that reads one element past this intermediate gets is the poison ...
+            past = torch.as_strided(t, (16,), (1,), t.storage_offset())[15]
+            assert int(past.view(torch.int32)) == word and bool(torch.isnan(past)) == (name == 'nan')
+            # ... and a stray store is still reported, also one that stores a NaN of other bits over a NaN guard (the comparison is of int32 words)
+            torch.as_strided(t, (16,), (1,), t.storage_offset())[15] = 2.0
+            assert g.check() == [{'function': rec.function, 'line': rec.line, 'shape': (3, 5), 'side': 'after', 'offset': 0, 'words': 1}]
+            rec.front[-1] = 0x7FC00001
+            assert sorted(v['side'] for v in g.check()) == ['after', 'before']
+    with ga.guarded(_Module, 'nan') as g:          # the default word is the one from before
+        _Module.torch.empty(3, dtype=torch.float32, device='cpu')
+        assert g.canary == ga.CANARY and bool((g.allocations[0].front == ga.CANARY).all())
+    with ga.guarded(_Module, 'nan', canary=0) as g:          # the neighbourhood of the 'zero' placement
+        _Module.torch.empty(3, dtype=torch.float32, device='cpu')
+        assert bool((g.allocations[0].back == 0).all()) and g.check() == []
+    with pytest.raises(ValueError):
+        ga.Guard('nan', canary=-1)
+
+
+def test_shift_exception_lists_are_explicit_and_small():
+    assert _SELECTION_ERROR is None, _SELECTION_ERROR
+    names = {c.name for c in CASES}
+    assert set(SHIFT_REORDERS) <= names and set(SHIFT_REFUSES) <= names and not set(SHIFT_REORDERS) & set(SHIFT_REFUSES)
+    assert 100 * (len(SHIFT_REORDERS) + len(SHIFT_REFUSES)) <= SHIFT_EXCEPTION_CAP * len(CASES), (len(SHIFT_REORDERS), len(SHIFT_REFUSES), len(CASES))
+    assert all(re.fullmatch(r'\w+\.hip:\d+', line) and outs for line, outs in SHIFT_REORDERS.values()), 'every reordering names the line that branches and the outputs it reaches'
+    assert all(SHIFT_REFUSES.values())
+    assert not any(c.same is not None and c.name in SHIFT_REORDERS for c in CASES)
+
+
+def test_scalar_offset_rule_case_stores_phantom_channels_into_its_guard():
+    """The case named as evidence for the range-check rule is in the table, runs conv_bf16x3_kernel with a 32-channel tile over N = 20, and the
+    planes its phantom channels would be stored to lie inside the trailing guard of the last sample's output."""
+    assert _SELECTION_ERROR is None, _SELECTION_ERROR
+    (mode, name, c, pitched), = [sel for sel in CONV_SELECTION if 'conv2d-%s-%s-%s' % (sel[0], sel[1], 'x'.join(map(str, sel[2]))) == SCALAR_OFFSET_RULE_CASE and not sel[3]]
+    b, K, N, h, w, k, up, down, pad = c
+    g = _conv_geom(c)
+    assert mode == 'bf16x3' and name.startswith('conv_bf16x3_kernel<1,4,1,') and K % 32 and N % 32 == 20 and b >= 2
+    assert 0 < (32 - N) * g.out_h * g.out_w * 4 <= ga.MIN_GUARD
+    assert SCALAR_OFFSET_RULE_CASE in {cs.name for cs in CASES}
+
+
 def launching_entries():
     """Every 'gc_...' string literal of op/_backend.py that names an exported symbol: the entries that launch (queries are called as attributes)."""
     with open(_backend.__file__) as f:
@@ -935,13 +1110,21 @@ def test_selection_reaches_every_kernel_variant():
 
 
 def test_case_table_stays_small():
-    """Device memory of the largest case, threefold (payload + two guards): well under 1 GiB."""
+    """Device memory of the largest case, threefold (payload + two guards): well under 1 GiB -- and still under it with the hostile copies of its
+    inputs, threefold as well (the smallest shape that reaches the main-region + edge kernel of the transposed convolution sets both figures)."""
     assert _SELECTION_ERROR is None, _SELECTION_ERROR
-    worst = 0
+    worst, with_inputs = 0, 0
     for mode, _, c, _ in CONV_SELECTION:
         g = _conv_geom(c)
-        worst = max(worst, 4 * c[0] * c[2] * g.out_h * _p32(g.out_w) * 2)          # two outputs per case
+        out = 4 * c[0] * c[2] * g.out_h * _p32(g.out_w)
+        worst = max(worst, out * 2)          # two outputs per case
+        inputs = 4 * (c[0] * c[1] * c[3] * _p32(c[4]) + c[5] * c[5] * c[1] * c[2]) + out          # x, the weights, the residual (scales, bias and noise: a plane's worth)
+        with_inputs = max(with_inputs, 3 * 2 * out + 3 * inputs)
+    for mode, _, c, _ in WGRAD_SELECTION:
+        g = _wgrad_geom(c)
+        with_inputs = max(with_inputs, 3 * 4 * c[0] * (c[1] * c[3] * _p32(c[4]) + c[2] * g.out_h * g.out_w))          # x and dy; the gradients are small next to them
     assert 3 * worst < (1 << 30) // 2, worst
+    assert with_inputs < 1 << 30, with_inputs
 
 
 # ====================================================================================================================================================
@@ -1019,6 +1202,86 @@ def _run_case(case, hip):
         assert torch.equal(_logical_bits(t), _logical_bits(before[n])), 'input %r was written' % n
 
 
+def _place(a, fill, shift):
+    """The inputs of a case, every tensor through hostile().  A row-pitched input keeps shift 0: _lib.row_pitch recognises only 16-byte-aligned ones."""
+    return {n: ga.hostile(t, fill, 0 if _lib.row_pitch(t) else shift) if torch.is_tensor(t) else t for n, t in a.items()}
+
+
+def _hostile_run(case, hip, a, fill, shift):
+    """One run of the case on hostile inputs inside a guarded context whose guards hold the same word -> its outputs.  No guard violation, the
+    entries reached, no byte of any input buffer written."""
+    placed = _place(a, fill, shift)
+    tag = '%s fill, shift %d' % (fill, shift)
+    with ga.guarded(_backend, fill if fill in ga.POISONS else 'nan', canary=ga.FILLS[fill]) as g:
+        outs = _flat(case.run(hip, placed, g))
+        violations = g.check()
+    assert not violations, '%s: stores outside the granted bytes (%s):\n%s' % (case.name, tag, '\n'.join(map(str, violations)))
+    assert case.entries <= set(g.entries), (sorted(case.entries - set(g.entries)), sorted(set(g.entries)))
+    for n, h in _tensors(placed).items():
+        changed = ga.hostile_changes(h, a[n])
+        assert changed is None, '%s: the buffer of input %r was written (%s): %s' % (case.name, n, tag, changed)
+    return outs
+
+
+def _same_as_plain(case, a, plain, outs, tag, tol=None, reordered=()):
+    """Every output finite and the plain run's bits (case.same where a case has one); the outputs listed in `reordered` within `tol` instead."""
+    assert len(outs) == len(plain)
+    for i, (p, o) in enumerate(zip(plain, outs)):
+        assert (o is None) == (p is None), '%s: output %d (%s)' % (case.name, i, tag)
+        if o is not None:
+            bad = int((~torch.isfinite(o)).sum())
+            assert not bad, '%s: output %d holds %d non-finite elements (%s): the entry used bytes outside an input' % (case.name, i, bad, tag)
+    if case.same is not None:
+        assert case.same(a, plain, outs), '%s (%s)' % (case.name, tag)
+        return
+    for i, (p, o) in enumerate(zip(plain, outs)):
+        if p is None:
+            continue
+        assert p.shape == o.shape
+        if i not in reordered:
+            assert torch.equal(o, p), '%s: output %d differs from the plain run in %d elements (%s): the entry used bytes outside an input, or depends on where the input lies' % (
+                case.name, i, int((o != p).sum()), tag)
+        else:
+            err = rel_err(o, _dbl(p))
+            print(case.name, 'output %d: %.3g against the plain run (bound %.3g)' % (i, err, tol))
+            assert err < tol, '%s: output %d is %.3g from the plain run, bound %.3g (%s)' % (case.name, i, err, tol, tag)
+
+
+def _run_hostile(case, hip):
+    """Plain, three fills, one shifted placement.  What this cannot see: a value from outside an input's ROW that lies inside the input, or beyond
+    the kernel's own per-sample descriptor.  With the right-edge mask of x_store (wgrad_bf16x3_ws2_kernel) taken out, the dense-x case of that
+    kernel still passes here on the MI355X: the words past a row end are the sample's own next row, the same in every placement, and past the
+    sample the range check returns zeros -- the fp64 comparisons of tests/test_ops_gpu.py are what catch that mutation.  A row-pitched input is
+    the placement in which a missing row-end mask meets the fill."""
+    a = case.build(DEV)
+    plain = _flat(case.run(hip, a, None))
+    for o in plain:
+        assert o is None or bool(torch.isfinite(o).all()), 'the plain run is not finite: the inputs are'
+    for fill in ('nan', 'big', 'zero'):
+        _same_as_plain(case, a, plain, _hostile_run(case, hip, a, fill, 0), '%s fill' % fill)
+    # 4 bytes off the 512-byte boundary: what autograd passes for a sample slice or a chunk of an odd-sized tensor
+    if case.name in SHIFT_REFUSES:
+        with pytest.raises(RuntimeError, match=re.escape(SHIFT_REFUSES[case.name])):
+            _hostile_run(case, hip, a, 'nan', 4)
+        return
+    _same_as_plain(case, a, plain, _hostile_run(case, hip, a, 'nan', 4), 'nan fill, shift 4', _TOL[case.mode or 'f32'], SHIFT_REORDERS.get(case.name, (None, ()))[1])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('case', CASES, ids=[c.name for c in CASES])
+def test_entry_on_hostile_inputs(case, hip):
+    prev = hip.conv_mode
+    hip.conv_mode = case.mode or 'f32'
+    try:
+        _run_hostile(case, hip)
+    except RuntimeError as e:
+        if 'illegal memory access' in str(e) or 'HIP error' in str(e):          # the context is lost: every later launch would fail, and none should be made
+            pytest.exit('GPU fault in case %s: %s' % (case.name, str(e).splitlines()[0]), returncode=3)
+        raise
+    finally:
+        hip.conv_mode = prev
+
+
 def _iteration(dev, size, batch):
     """One D step, R1, G step and path-length step of a FRESH trainer (its weight packs happen in here): losses and the gradients of every pass."""
     import op_checks as oc
@@ -1055,9 +1318,9 @@ def _iteration(dev, size, batch):
 @pytest.mark.gpu
 def test_whole_iteration_on_guarded_buffers(hip):
     """One discriminator and one generator iteration with both regularisers (R1, path length: the second-order entries), split-bf16, 128 x 128, batch 2 --
-    the smallest resolution at which outputs are row-pitched (out_w >= 129) -- plain and under NaN poison: no guard violation, every loss and every
-    parameter gradient finite and bit-identical to the plain run's.  Both halves run: measured on the MI355X, the plain iteration takes 2.0 s (trainer
-    construction included) and the guarded one 0.8 s.  The harness keeps all 3269 allocations of the iteration alive until check(): 23 GiB of payload,
+    the smallest resolution at which outputs are row-pitched (out_w >= 129) -- plain, under NaN poison, and with NaN and then 1e30 both as the poison
+    and in the guards of every allocation: no guard violation, every loss and every parameter gradient finite and bit-identical to the plain run's.  Every part runs: measured on the MI355X, the plain iteration takes 2.0 s (trainer
+    construction included) and each guarded one 0.7 - 0.8 s.  The harness keeps all 3269 allocations of the iteration alive until check(): 23 GiB of payload,
     three times that with the guards -- device memory the MI355X has, and released when the test ends."""
     from gan_control_amd.models.op import weight_cache
     prev, hip.conv_mode = hip.conv_mode, 'bf16x3'
@@ -1083,6 +1346,21 @@ def test_whole_iteration_on_guarded_buffers(hip):
         for k, v in plain.items():
             assert bool(torch.isfinite(got[k]).all()), k
             assert torch.equal(got[k], v), k
+        # ... and with the poison in the GUARDS too: every intermediate then reaches the kernel that reads it between NaN, or between 1e30
+        del got, g
+        for poison in ('nan', 'big'):
+            t2 = time.time()
+            with ga.guarded(_backend, poison, canary=ga.POISONS[poison]) as g:
+                got = _iteration(DEV, 128, 2)
+                violations = g.check()
+            weight_cache.clear()
+            print('whole iteration, %s in the guards: %.1f s' % (poison, time.time() - t2))
+            assert not violations, 'stores outside the granted bytes (%s in the guards):\n%s' % (poison, '\n'.join(map(str, violations[:20])))
+            assert sorted(got) == sorted(plain)
+            for k, v in plain.items():
+                assert bool(torch.isfinite(got[k]).all()), (poison, k)
+                assert torch.equal(got[k], v), (poison, k)
+            del got, g
     finally:
         hip.conv_mode = prev
         torch.cuda.empty_cache()
