@@ -128,6 +128,9 @@ SIGNATURES = {
     'gc_se_apply_f32': (_i32, [_vp] * 4 + [_i32] * 6 + [_vp]),
     'gc_weight_layout_grouped_f32': (_i32, [ctypes.POINTER(WLayoutGroup), _i32, _vp]),
     'gc_conv2d_pack_weights_bf16x3_grouped': (_i32, [ctypes.POINTER(WPackGroup), _i32, _vp]),
+    'gc_image_u8_to_f32': (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    'gc_image_resample_u8': (_i32, [_vp, _i64, _i64, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    'gc_image_resample_v_u8_to_f32': (_i32, [_vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
     'gc_weight_layout_f32': (_i32, [_vp, _vp, _i32, _i32, _i32, ctypes.POINTER(_i64 * 3), ctypes.POINTER(_i64 * 3), _i32, _f32, _vp]),
 }
 

@@ -1,0 +1,34 @@
+"""Inception statistics of a folder of REAL images: the {'mean', 'cov'} pickle ``fid.evaluate_fid`` compares generated images against.
+
+Reference: fid_utils/calc_inception.py:61-80 (``extract_features``: every batch of the loader through ``inception(img)[0]``, flattened per
+image, collected on the host) and its ``__main__`` (mean and ``np.cov`` of the features, pickled).  The batches come from a
+``datasets.image_folder.DeviceImageStream`` built with ``training=False``: no flip and no crop, as the reference's transform for this job.
+"""
+import pickle
+
+import torch
+
+from .fid import feature_statistics
+
+
+@torch.no_grad()
+def extract_real_features(stream, feature_net, n_images):
+    """float32 [n_images, F] on the host: ``feature_net(img)[0]`` per batch of ``stream`` (an iterator of ``(img, meta)``), in stream order."""
+    if getattr(stream, 'training', False):
+        raise ValueError('real statistics are taken without flip or crop: build the stream with training=False')
+    feats, have = [], 0
+    while have < n_images:
+        img, _ = next(stream)
+        f = feature_net(img)[0]
+        feats.append(f.reshape(img.shape[0], -1).to('cpu'))
+        have += img.shape[0]
+    return torch.cat(feats, 0)[:n_images]
+
+
+def save_real_statistics(path, features):
+    """Pickle {'mean', 'cov'} of a [n, F] feature matrix where ``evaluate_fid(..., inception_stat_path=path)`` reads it."""
+    f = features.double().numpy() if torch.is_tensor(features) else features
+    mean, cov = feature_statistics(f)
+    with open(path, 'wb') as fh:
+        pickle.dump({'mean': mean, 'cov': cov}, fh)
+    return mean, cov

@@ -475,6 +475,18 @@ class GeneratorTrainer:
                 out[k] = float(v)
         return out
 
+    def make_data_stream(self, data_config, seed=0, **kw):
+        """The real-image stream of this rank for ``train(data=stream.images())``, picked by ``data_config['data_set_name']`` as init_data_set
+        does (generator_trainer.py:205-216): the decode runs in workers, everything after it on the device (datasets/image_folder.py)."""
+        from ..datasets import image_folder
+        loaders = {'ffhq': image_folder.get_ffhq_data_loader, 'afhq': image_folder.get_afhq_data_loader,
+                   'met-faces': image_folder.get_metfaces_data_loader}
+        name = data_config['data_set_name']
+        if name not in loaders:
+            raise ValueError('data_config[data_set_name] = %s (not valid)' % name)
+        return loaders[name](data_config, batch_size=self.local_batch, size=self.model_config['size'], training=True, device=self.device,
+                             seed=seed, rank=self.rank, world=self.world, **kw)
+
     def synthetic_batch(self):
         """FFHQ-shaped stand-in for the data loader: float32 NCHW uniform in [-1, 1] (ffhq_dataset.py:62-63)."""
         mc = self.model_config

@@ -577,6 +577,45 @@ int gc_se_mlp_bwd_f32(const float* t, const float* s, const float* z, const floa
 int gc_se_apply_f32(const float* r, const float* s, const float* sc, float* out, int planes, int h, int w, int sc_h, int sc_w, int sc_stride,
                     gc_stream_t stream);
 
+/* ---- the real-image input path after the decode (datasets/image_ops.py, csrc/image_input.hip) ----------------------------------------
+ * The reference builds a training batch on the host, in DataLoader workers: PIL decode, transforms.Resize (FFHQ, MetFaces:
+ * ffhq_dataset.py:56-64) or RandomResizedCrop + Resize (AFHQ: afhq_dataset.py:50-59), RandomHorizontalFlip, ToTensor, Normalize(0.5, 0.5),
+ * and moves float32 to the device.  Here the workers hand over the decoded uint8 [B, H, W, 3] and these three entries do the rest, with the
+ * same bits: the resize is PIL's 8-bit bilinear resample (two separable passes with 22-bit fixed-point coefficients and a uint8
+ * intermediate), the normalisation a 256-entry table the host fills with the reference's own float32 operation sequence.
+ *
+ * Common to all three: x is interleaved uint8, pixel (b, i, j) at x + b * sample_stride + i * row_stride + 3 * j (strides in BYTES, any
+ * alignment: a view of a larger buffer); lut 256 floats and flip `batch` int32, both on the device; outputs are dense.  No byte of x
+ * outside the pixels named below influences the result.  Bad arguments (null pointers, kmax < 1, tables that reach outside the input)
+ * return GC_ERR_BAD_ARG and launch nothing.
+ *
+ * gc_image_u8_to_f32: y [batch, 3, h, w], y[b, c, i, j] = lut[x[b, i, jj, c]], jj = w - 1 - j where flip[b] != 0, else j.  One launch.
+ *
+ * gc_image_resample_u8: one resample pass along one axis, uint8 -> uint8: y [batch, out_h, out_w, 3].
+ *   axis 0 (horizontal): y[b, r, o, c] = P(x[b, off_b + r, first + k, c]) for r < count_b;   axis 1 (vertical): y[b, o, q, c] =
+ *   P(x[b, first + k, off_b + q, c]) for q < count_b, where for output index o (first, taps) = bounds[s, o, :] and
+ *   P = clamp((2^21 + sum_{k < taps} pixel_k * coeff[s, o, k]) >> 22, 0, 255) in int32.  coeff int32 [S, out, kmax], bounds int32
+ *   [S, out, 2] on the device; s = b * table_stride with table_stride 0 (S = 1: every sample shares the tables) or 1 (S = batch: per-sample
+ *   crops).  `first` already includes the crop offset; coefficient slots at or past `taps` are never read.  other int32 [S, 2] on the device
+ *   = (off, count) along the axis that is NOT resampled (the crop there; rows / columns of y at or past count are not produced), or NULL
+ *   for (0, the output extent).  bounds_host / other_host are HOST copies of the two tables: they are what the entry validates before the
+ *   launch (first >= 0, 1 <= taps <= kmax, first + taps <= the input extent; off + count inside the input, count <= the output extent);
+ *   the kernels clamp what they read from the device copies to the same limits, so a device table that differs cannot read outside x.
+ *
+ * gc_image_resample_v_u8_to_f32: the vertical pass fused with the table lookup, the flip and the planar store:
+ *   y [batch, 3, out_h, out_w], y[b, c, o, j] = lut[P(x[b, first + k, off_b + jj, c])], jj mirrored within the out_w columns where flip[b].
+ *   Arguments as above (axis 1); other's count must be out_w.
+ * A resize is gc_image_resample_u8(axis 0) into a uint8 intermediate followed by this entry: two launches, no float intermediate. */
+int gc_image_u8_to_f32(const uint8_t* x, int64_t row_stride, int64_t sample_stride, const float* lut, const int32_t* flip, float* y,
+                       int batch, int h, int w, gc_stream_t stream);
+int gc_image_resample_u8(const uint8_t* x, int64_t row_stride, int64_t sample_stride, int in_h, int in_w, uint8_t* y, int batch,
+                         int out_h, int out_w, int axis, const int32_t* coeff, const int32_t* bounds, const int32_t* bounds_host,
+                         int kmax, int table_stride, const int32_t* other, const int32_t* other_host, gc_stream_t stream);
+int gc_image_resample_v_u8_to_f32(const uint8_t* x, int64_t row_stride, int64_t sample_stride, int in_h, int in_w, const float* lut,
+                                  const int32_t* flip, float* y, int batch, int out_h, int out_w, const int32_t* coeff,
+                                  const int32_t* bounds, const int32_t* bounds_host, int kmax, int table_stride, const int32_t* other,
+                                  const int32_t* other_host, gc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
