@@ -131,6 +131,7 @@ SIGNATURES = {
     'gc_image_u8_to_f32': (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     'gc_image_resample_u8': (_i32, [_vp, _i64, _i64, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
     'gc_image_resample_v_u8_to_f32': (_i32, [_vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    'gc_image_f32_to_u8_grid': (_i32, [_vp, _i64, _i64, _i64, _vp, _i64] + [_i32] * 8 + [_vp]),
     'gc_weight_layout_f32': (_i32, [_vp, _vp, _i32, _i32, _i32, ctypes.POINTER(_i64 * 3), ctypes.POINTER(_i64 * 3), _i32, _f32, _vp]),
 }
 

@@ -439,12 +439,72 @@ class GeneratorTrainer:
             torch.save(self.state_dict(), path)
         return path
 
-    def train(self, data=None, save_dir=None, iters=None, start_iter=None, save_every=None, on_iteration=None):
+    # -- what a run shows for itself (init_evaluation :264-299, end_iter_update :721-733, save_images :774-850) ----------------------
+    def make_tracker(self, inception=None, n_samples=16, seed=0):
+        """The evaluation.Tracker of this run: ``n_samples`` fixed latents and injection noises on the host, drawn once from ``seed`` (the
+        reference draws them in its constructor, :65-75), ``inception`` for FID and ``config['evaluation_config']['fid']`` when there is one."""
+        from ..evaluation.tracker import Tracker
+        gen = torch.Generator().manual_seed(seed)
+        latents = torch.randn(n_samples, self.model_config['latent_size'], generator=gen)
+        noises = [torch.randn(n_samples, 1, 4, 4, generator=gen)]
+        for i in range(3, self.generator.log_size + 1):
+            noises += [torch.randn(n_samples, 1, 2 ** i, 2 ** i, generator=gen) for _ in range(2)]
+        fid_config = (self.config.get('evaluation_config') or {}).get('fid')
+        return Tracker(latents, noises, inception, self.model_config.get('g_noise_mode', 'normal'), fid_config=fid_config)
+
+    def save_matrix(self, matrix_path, same_chunk_group, i, tracker, same_noise_for_all=False):
+        size = self.model_config['size']
+        image = tracker.make_matrix(self.g_ema, downsample=size // 256 if size >= 256 else None,          # (the reference divides by zero below 256)
+                                    same_chunk=self.batch_utils.place_in_latent_dict[same_chunk_group], same_noise_for_all=same_noise_for_all)
+        os.makedirs(matrix_path, exist_ok=True)
+        path = os.path.join(matrix_path, '%s.jpg' % str(i).zfill(6))
+        image.save(path)
+        return path
+
+    def save_images(self, i, save_dir, tracker):
+        """The files of the reference's save_images under its names: ``images/sample/<i:06d>.png`` and, when the run has sub-latent groups
+        (``batch_utils``), ``images/matrix[_same_noise]/<i:06d>.jpg`` on the ``embedding_loss`` group plus ``images/default_<group>_matrix
+        [_same_noise]`` for every group.  A vanilla model has no groups: the sample grid only.  Rank 0 writes; -> the paths written."""
+        if self.rank != 0:
+            return []
+        root = os.path.join(save_dir, 'images')
+        self.g_ema.eval()
+        os.makedirs(os.path.join(root, 'sample'), exist_ok=True)
+        written = [os.path.join(root, 'sample', '%s.png' % str(i).zfill(6))]
+        tracker.make_samples(self.g_ema).save(written[0])
+        if self.batch_utils is None:
+            return written
+        emb = (self.training_config.get('embedding_loss') or {}).get('same_group_name')
+        if emb is not None:
+            written.append(self.save_matrix(os.path.join(root, 'matrix'), emb, i, tracker))
+            written.append(self.save_matrix(os.path.join(root, 'matrix_same_noise'), emb, i, tracker, same_noise_for_all=True))
+        for group_name in self.batch_utils.get_ordered_group_names():
+            written.append(self.save_matrix(os.path.join(root, 'default_%s_matrix' % group_name), group_name, i, tracker))
+            written.append(self.save_matrix(os.path.join(root, 'default_%s_matrix_same_noise' % group_name), group_name, i, tracker,
+                                            same_noise_for_all=True))
+        return written
+
+    def _end_iter_evaluation(self, i, save_dir, tracker):
+        """evaluate and save_images of end_iter_update (:724-727) on rank 0; an interval that is missing or 0 never fires."""
+        if self.rank != 0:
+            return
+        tc = self.training_config
+        debug = tc.get('debug', False)
+        every = tc.get('min_evaluate_interval', 0)
+        if (every and i % every == 0) or (debug and i % 10 == 0):
+            tracker.evaluate(i, self.g_ema, debug=debug, graph_save_path=None if save_dir is None else os.path.join(save_dir, 'graphs'))
+        every = tc.get('save_images_interval', 0)
+        if save_dir is not None and ((every and i % every == 0) or (debug and i % 100 == 0)):
+            self.save_images(i, save_dir, tracker)
+
+    def train(self, data=None, save_dir=None, iters=None, start_iter=None, save_every=None, on_iteration=None, tracker=None):
         """The loop of the reference's ``train()`` (generator_trainer.py:329-355): for i in start_iter .. iter: discriminator_update(i),
         generator_update(i), then the checkpoint cadence of end_iter_update (:728-731: ``i % save_nets_interval == 0``).  ``data`` is an iterator
-        of real batches already on the device (this rank's shard; None = a resident synthetic batch, what bench.py times); evaluation, image
-        grids, tensorboard and the CSV monitor of end_iter_update are outside the hot path and left to ``on_iteration(i, trainer)``.
-        Returns the iteration counter after the last step."""
+        of real batches already on the device (this rank's shard; None = a resident synthetic batch, what bench.py times).  With a ``tracker``
+        (make_tracker) every iteration ends with the rest of end_iter_update's cadence on rank 0: ``min_evaluate_interval`` -> tracker.evaluate
+        (FID), ``save_images_interval`` -> save_images, and ``best_fid.pt`` next to a periodic checkpoint when FID is enabled and the last FID is
+        the best so far.  Tensorboard and the CSV monitor are left to ``on_iteration(i, trainer)``.  Returns the iteration counter after the
+        last step."""
         tc = self.training_config
         iters = tc.get('iter', 0) if iters is None else iters
         start = tc.get('start_iter', 0) if start_iter is None else start_iter
@@ -458,8 +518,12 @@ class GeneratorTrainer:
             batch = next(data) if data is not None else real
             self.discriminator_update(i, batch)
             self.generator_update(i)
+            if tracker is not None:
+                self._end_iter_evaluation(i, save_dir, tracker)
             if save_dir is not None and every and i % every == 0 and not tc.get('debug', False):
                 self.save_nets(i, save_dir)
+                if tracker is not None and tracker.fid_config.get('enabled') and tracker.is_best_fid():
+                    self.save_nets(i, save_dir, best_fid=True)
             if on_iteration is not None:
                 on_iteration(i, self)
             nxt = i + 1

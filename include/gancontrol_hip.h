@@ -616,6 +616,30 @@ int gc_image_resample_v_u8_to_f32(const uint8_t* x, int64_t row_stride, int64_t 
                                   const int32_t* bounds, const int32_t* bounds_host, int kmax, int table_stride, const int32_t* other,
                                   const int32_t* other_host, gc_stream_t stream);
 
+/* ---- the image output path (evaluation/image_grid.py, csrc/image_output.hip) ------------------------------------------------------------
+ * The mirror image of the entries above: float32 planar images in [-1, 1] -> ONE uint8 interleaved image grid, in one launch.  It stands for
+ * the reference's host chain t.mul(0.5).add(0.5).clamp(min=0., max=1.) -> torchvision.utils.make_grid -> ToPILImage (mul(255).byte())
+ * (evaluation/generation.py:14-22, :87-94), with the same bytes.
+ *
+ * x: float32 [batch, 3, h, w] on the device, element (b, c, i, j) at x + b * sample_stride + c * plane_stride + i * row_stride + j (strides in
+ * ELEMENTS, at least dense: row_stride >= w, plane_stride >= (h - 1) * row_stride + w, sample_stride >= 2 * plane_stride + (h - 1) * row_stride
+ * + w; a slice of a larger batch or rows with a pitch are fine).  y: uint8 [grid_h, grid_w, 3] on the device, byte (r, q, c) at
+ * y + r * y_row_stride + 3 * q + c (y_row_stride in BYTES, >= 3 * grid_w; y may start at any byte).
+ *
+ * Geometry (make_grid's): xmaps = min(nrow, batch), ymaps = ceil(batch / xmaps), grid_h = ymaps * (h + padding) + padding, grid_w = xmaps *
+ * (w + padding) + padding; tile k occupies rows (k / xmaps) * (h + padding) + padding + [0, h) and columns (k % xmaps) * (w + padding) +
+ * padding + [0, w).  The caller passes grid_h and grid_w; they are recomputed here and a mismatch is refused.  nrow 1 with padding 0 gives
+ * [batch * h, w, 3]: a dense uint8 [batch, h, w, 3].
+ *
+ * A tile byte is trunc(v4), v1 = x * 0.5f, v2 = v1 + 0.5f, v3 = min(max(v2, 0), 1), v4 = v3 * 255.0f, every step rounded to float32 on its own
+ * (x * 127.5f + 127.5f is another function: it differs on 223 of the 510 floats next to a byte boundary).  +-inf follow the clamp (255 / 0);
+ * NaN gives byte 0.  Every other byte of the grid -- the padding bands and the empty tiles of a ragged last row -- is pad_value (0 .. 255).
+ * Every byte of y[0:grid_h, 0:3 * grid_w] is stored exactly once (y may be uninitialised), nothing else is stored, and nothing outside the
+ * batch * 3 * h * w floats named above is loaded.  Null pointers, non-positive extents, padding < 0, a pad_value outside a byte, grid_h /
+ * grid_w that differ from the geometry and short strides return GC_ERR_BAD_ARG and launch nothing. */
+int gc_image_f32_to_u8_grid(const float* x, int64_t row_stride, int64_t plane_stride, int64_t sample_stride, uint8_t* y, int64_t y_row_stride,
+                            int batch, int h, int w, int nrow, int padding, int pad_value, int grid_h, int grid_w, gc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
