@@ -88,6 +88,70 @@ __global__ __launch_bounds__(256) void bias_act_bwd_kernel(
     }
 }
 
+// Activation backward with the NOISE-MAP gradient taken in the same pass (gc_bias_act_bwd_noise_f32):
+//   g_pre = MASK ? dy * mask(y_ref) : dy;   dx = g_pre (MASK only);   dnoise[b, i] = noise_w * sum_c g_pre[b, c, i]
+// A lane owns four consecutive pixels of one sample (one 16-byte access per channel; the base need only be 4-byte aligned; the last lane of a
+// plane whose size is no multiple of 4 takes its 1..3 pixels one by one) and walks the channels in ascending order.  CS = 4 (few pixels,
+// many channels: the low resolutions) gives wave k the channels k, k + 4, ... and adds the four slices as (s0 + s1) + (s2 + s3) through LDS.
+// Either way the order of every sum is fixed by the shape alone: no atomics, the same bits every time.
+template <bool MASK, int CS>
+__global__ __launch_bounds__(256) void bias_act_bwd_noise_kernel(
+    const float* __restrict__ dy, const float* __restrict__ yref, const float* __restrict__ noise_w, float* __restrict__ dx,
+    float* __restrict__ dnoise, int channels, int64_t inner, int64_t quads, float pos, float neg) {
+#pragma clang fp contract(off)          // the sums add the ROUNDED g_pre that is stored to dx (no fma of dy * mask into the sum): both forms give the same bits
+    __shared__ float lds[CS > 1 ? 3 * 256 : 1];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t q = CS == 1 ? (int64_t)blockIdx.x * 256 + threadIdx.x : (int64_t)blockIdx.x * 64 + lane;
+    const int b = blockIdx.y;
+    const int64_t i0 = 4 * q;
+    const int cnt = q < quads ? (int)min((int64_t)4, inner - i0) : 0;
+    float s[4] = {0.f, 0.f, 0.f, 0.f};
+    if (cnt == 4) {
+#pragma unroll 4
+        for (int c = CS == 1 ? 0 : wave; c < channels; c += CS) {
+            const size_t off = ((size_t)b * channels + c) * inner + i0;
+            gc::f32x4u_t g = gc::stream_load4u(dy + off);
+            if (MASK) {
+                const gc::f32x4u_t r = gc::stream_load4u(yref + off);
+                g.x = g.x * (r.x > 0.f ? pos : neg); g.y = g.y * (r.y > 0.f ? pos : neg);
+                g.z = g.z * (r.z > 0.f ? pos : neg); g.w = g.w * (r.w > 0.f ? pos : neg);
+                gc::stream_store4u(dx + off, g.x, g.y, g.z, g.w);
+            }
+            s[0] += g.x; s[1] += g.y; s[2] += g.z; s[3] += g.w;
+        }
+    } else if (cnt > 0) {
+        for (int c = CS == 1 ? 0 : wave; c < channels; c += CS) {
+            const size_t off = ((size_t)b * channels + c) * inner + i0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                if (k < cnt) {
+                    float g = dy[off + k];
+                    if (MASK) { g = g * (yref[off + k] > 0.f ? pos : neg); dx[off + k] = g; }
+                    s[k] += g;
+                }
+        }
+    }
+    if (CS > 1) {
+        if (wave > 0) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) lds[(wave - 1) * 256 + 4 * lane + k] = s[k];
+        }
+        __syncthreads();
+        if (wave > 0) return;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) s[k] = (s[k] + lds[4 * lane + k]) + (lds[256 + 4 * lane + k] + lds[512 + 4 * lane + k]);
+    }
+    const float nw = noise_w[0];
+    float* out = dnoise + (size_t)b * inner + i0;
+    if (cnt == 4) {
+        *reinterpret_cast<gc::f32x4u_t*>(out) = gc::f32x4u_t{nw * s[0], nw * s[1], nw * s[2], nw * s[3]};
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            if (k < cnt) out[k] = nw * s[k];
+    }
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
@@ -377,6 +441,27 @@ extern "C" int gc_bias_act_bwd_f32(const float* dy, const float* y_ref, float* d
     else
         hipLaunchKernelGGL(bias_act_bwd_kernel<false>, dim3(blocks), dim3(256), 0, s, dy, y_ref, dx, count, gain, gain * slope);
     return gc::check_launch("gc_bias_act_bwd_f32");
+}
+
+extern "C" int gc_bias_act_bwd_noise_f32(const float* dy, const float* y_ref, const float* noise_w, float* dx, float* dnoise,
+                                         int batch, int channels, int64_t inner, float slope, float gain, gc_stream_t stream) {
+    const char* what = "gc_bias_act_bwd_noise_f32";
+    if (!dy || !noise_w || !dnoise) return gc::fail(GC_ERR_BAD_ARG, "%s: null pointer", what);
+    if (y_ref && !dx) return gc::fail(GC_ERR_BAD_ARG, "%s: y_ref without dx (null pointer)", what);
+    if (batch <= 0 || channels <= 0 || inner <= 0) return gc::fail(GC_ERR_BAD_ARG, "%s: bad extents", what);
+    if (batch > 65535) return gc::fail(GC_ERR_UNSUPPORTED, "%s: batch %d > 65535", what, batch);
+    const int64_t quads = gc::ceil_div64(inner, 4);
+    // few pixels and many channels (the low resolutions): the four waves of a workgroup share the channels of 64 pixel groups
+    const bool split = channels >= 8 && (int64_t)batch * quads < 64 * 2048;
+    const int64_t blocks = gc::ceil_div64(quads, split ? 64 : 256);
+    if (blocks > INT32_MAX) return gc::fail(GC_ERR_UNSUPPORTED, "%s: more than 2^31 blocks", what);
+    const dim3 grid((unsigned)blocks, (unsigned)batch);
+    hipStream_t s = (hipStream_t)stream;
+#define GC_LAUNCH(M, C) hipLaunchKernelGGL((bias_act_bwd_noise_kernel<M, C>), grid, dim3(256), 0, s, dy, y_ref, noise_w, dx, dnoise, channels, inner, quads, gain, gain * slope)
+    if (y_ref) { if (split) GC_LAUNCH(true, 4); else GC_LAUNCH(true, 1); }
+    else       { if (split) GC_LAUNCH(false, 4); else GC_LAUNCH(false, 1); }
+#undef GC_LAUNCH
+    return gc::check_launch(what);
 }
 
 extern "C" size_t gc_channel_sum_workspace(int batch, int channels, int64_t inner) {

@@ -62,6 +62,7 @@ SIGNATURES = {
     'gc_upfirdn2d_act_f32': (_i32, [_vp, _vp, _vp] + [_i32] * 11 + [_vp, _vp, _vp, _f32, _f32, _vp]),
     'gc_bias_act_f32': (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _f32, _f32, _vp]),
     'gc_bias_act_bwd_f32': (_i32, [_vp, _vp, _vp, _i64, _f32, _f32, _vp]),
+    'gc_bias_act_bwd_noise_f32': (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _f32, _f32, _vp]),
     'gc_bias_act_bwd_chunks': (_i32, [_i64]),
     'gc_bias_act_bwd_reduce_f32': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _f32, _f32, _vp]),
     'gc_bias_act_bwd_reduce_self_f32': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _f32, _f32, _vp]),
@@ -132,6 +133,11 @@ SIGNATURES = {
     'gc_image_resample_u8': (_i32, [_vp, _i64, _i64, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
     'gc_image_resample_v_u8_to_f32': (_i32, [_vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
     'gc_image_f32_to_u8_grid': (_i32, [_vp, _i64, _i64, _i64, _vp, _i64] + [_i32] * 8 + [_vp]),
+    'gc_noise_reg_workspace': (_sz, [_vp, _vp, _i32]),
+    'gc_noise_reg_fwd_f32': (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _sz, _vp]),
+    'gc_noise_reg_bwd_f32': (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
+    'gc_noise_normalize_workspace': (_sz, [_vp, _i32]),
+    'gc_noise_normalize_f32': (_i32, [_vp, _vp, _i32, _vp, _sz, _vp]),
     'gc_weight_layout_f32': (_i32, [_vp, _vp, _i32, _i32, _i32, ctypes.POINTER(_i64 * 3), ctypes.POINTER(_i64 * 3), _i32, _f32, _vp]),
 }
 

@@ -316,16 +316,18 @@ class _ModConvAct(Function):
     @staticmethod
     def backward(ctx, gy):
         from .fused_act import _BiasActGrad, _BiasActGradReduce
+        from . import noise_grad
         x, w_t, si, so, bias, noise, noise_w, out = ctx.saved_tensors
         has_si, has_so, has_bias, has_noise = ctx.has
         si, so, bias = (si if has_si else None), (so if has_so else None), (bias if has_bias else None)
         noise, noise_w = (noise, noise_w) if has_noise else (None, None)
         g, (slope, gain) = ctx.geom, ctx.cfg
         need = ctx.needs_input_grad
-        gx = gw = gsi = gso = gb = gnw = None
+        gx = gw = gsi = gso = gb = gnw = gn = None
         if gy is None or not any(need[:7]):
             return (None,) * 10
         want_so = has_so and need[3]
+        want_n = has_noise and need[5]              # the noise MAP (image projection); training never asks
         if not _backend.want_param_grads():
             need = list(need)
             need[1] = need[4] = need[6] = False          # weight, bias, noise strength
@@ -337,8 +339,16 @@ class _ModConvAct(Function):
                 gnw = pdot.sum().reshape(noise_w.shape)
             if want_so:
                 gso = _backend.call(_SumDiv, pself, so)
+            if want_n:
+                gn = noise_grad.pixel_sums_once(g_pre, noise_w)
+        elif want_n and not torch.is_grad_enabled():
+            g_pre, gn = noise_grad.masked(gy, out, noise_w, slope, gain)          # g_pre and its pixel sums from one pass over gy and out
         else:
             g_pre = _backend.call(_BiasActGrad, gy, out, slope, gain)
+            if want_n:
+                gn = noise_grad.pixel_sums_once(g_pre, noise_w)
+        if gn is not None:
+            gn = gn.reshape(noise.shape)
         need_si = has_si and need[2]
         fused = need[1] and _samples_route(x, g_pre, g, need_si, False)
         if need[0] or (need_si and not fused):
@@ -349,7 +359,7 @@ class _ModConvAct(Function):
             gw = _mod_weight_grad(x, g_pre, si, so, g)
         if need_si and not fused:
             gsi = _backend.call(_PlaneDot, x, gx, si)
-        return (gx if need[0] else None), gw, gsi, gso, gb, None, gnw, None, None, None
+        return (gx if need[0] else None), gw, gsi, gso, gb, gn, gnw, None, None, None
 
 
 def _swapped_geom(g, x):

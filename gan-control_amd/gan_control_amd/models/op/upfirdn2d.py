@@ -160,16 +160,18 @@ class _UpFirDn2dAct(Function):
         kernel, out, noise, noise_w = ctx.saved_tensors
         slope, gain = ctx.act
         need = ctx.needs_input_grad
-        gx = gb = gnw = None
+        from . import noise_grad
+        gx = gb = gnw = gn = None
         params = _backend.want_param_grads()
         want_b, want_nw = ctx.has_bias and need[4] and params, ctx.has_noise and need[6] and params
-        if gy is None or not (need[0] or want_b or want_nw):
+        want_n = ctx.has_noise and need[5]          # the noise MAP (image projection); training never asks
+        if gy is None or not (need[0] or want_b or want_nw or want_n):
             return (None,) * 9
         be = _backend.get()
         up, down, p0, p1, h, w = ctx.cfg
         kh, kw = kernel.shape
         fused = getattr(be, 'upfirdn2d_actbwd', None)
-        if (fused is not None and _FUSE_ACT_BWD and need[0] and not torch.is_grad_enabled() and not _backend.strict_zeros()
+        if (fused is not None and _FUSE_ACT_BWD and need[0] and not want_n and not torch.is_grad_enabled() and not _backend.strict_zeros()
                 and gy.is_contiguous() and out.is_contiguous() and 0 <= p0 <= min(kh, kw) - 1
                 and be.upfirdn2d_act_supported(kernel, 1, 1, h, w, gy.shape[0] * gy.shape[1])):
             # plain (not differentiated further) backward: activation backward, both reductions and the Blur adjoint in ONE pass over gy --
@@ -186,11 +188,20 @@ class _UpFirDn2dAct(Function):
                 gb = psum.sum((0, 2))
             if want_nw:
                 gnw = pdot.sum().reshape(noise_w.shape)
+            if want_n:
+                gn = noise_grad.pixel_sums_once(g_pre, noise_w)
+        elif want_n and not torch.is_grad_enabled():
+            # the pre-activation gradient has to exist for its pixel sums: the Function route, with the sums taken in the pass that makes it
+            g_pre, gn = noise_grad.masked(gy, out, noise_w, slope, gain)
         else:
             g_pre = _backend.call(_BiasActGrad, gy, out, slope, gain)
+            if want_n:
+                gn = noise_grad.pixel_sums_once(g_pre, noise_w)
+        if gn is not None:
+            gn = gn.reshape(noise.shape)
         if need[0]:
             gx = _backend.call(_UpFirDn2dAdjoint, g_pre, kernel, ctx.cfg)
-        return gx, None, None, None, gb, None, gnw, None, None
+        return gx, None, None, None, gb, gn, gnw, None, None
 
 
 def upfirdn2d_bias_act(input, kernel, pad, bias, noise=None, noise_weight=None, negative_slope=0.2, scale=2 ** 0.5):

@@ -138,6 +138,19 @@ int gc_bias_act_f32(const float* x, const float* bias, const float* noise, const
 int gc_bias_act_bwd_f32(const float* dy, const float* y_ref, float* dx, int64_t count,
                         float slope, float gain, gc_stream_t stream);
 
+/* The same gradient with the NOISE-MAP gradient taken in the same pass: what image projection needs, where the per-layer noise maps are
+ * optimised (reference: projection/projection.py; the injection itself is NoiseInjection, gan_model.py:334-345):
+ *   g_pre[b,c,i] = dy[b,c,i] * (y_ref[b,c,i] > 0 ? gain : gain * slope);   dx = g_pre  (the bits of gc_bias_act_bwd_f32)
+ *   dnoise[b,i]  = noise_w[0] * sum_c g_pre[b,c,i]
+ * dy and y_ref are read once.  With y_ref == NULL, dy is taken as an already computed g_pre: nothing is stored to dx (it may be NULL) and only
+ * the pixel sums are made -- for callers whose reduce pass (gc_bias_act_bwd_reduce_self_f32) has produced g_pre already.  The channels are
+ * added in an order fixed by the shape (ascending; where a plane has few pixels, four interleaved channel slices added as (s0 + s1) +
+ * (s2 + s3)): no atomics, the same bits for the same inputs.  noise_w is a DEVICE scalar.  16-byte accesses wherever four pixels of a plane
+ * remain, the ragged tail per element; every base need only be 4-byte aligned.  Null dy / noise_w / dnoise, y_ref without dx and
+ * non-positive extents return GC_ERR_BAD_ARG, batch > 65535 GC_ERR_UNSUPPORTED; neither launches anything. */
+int gc_bias_act_bwd_noise_f32(const float* dy, const float* y_ref, const float* noise_w, float* dx, float* dnoise,
+                              int batch, int channels, int64_t inner, float slope, float gain, gc_stream_t stream);
+
 /* The same gradient fused with the reductions its caller needs (one pass instead of three):
  *   dx = dy * mask(y_ref);   psum[(b*C + c)*chunks + j] = sum over chunk j of dx[b,c,:]
  *   pdot[(b*C + c)*chunks + j] = sum over chunk j of dx[b,c,:] * noise[b,:]      (only when noise != null)
@@ -639,6 +652,34 @@ int gc_image_resample_v_u8_to_f32(const uint8_t* x, int64_t row_stride, int64_t 
  * grid_w that differ from the geometry and short strides return GC_ERR_BAD_ARG and launch nothing. */
 int gc_image_f32_to_u8_grid(const float* x, int64_t row_stride, int64_t plane_stride, int64_t sample_stride, uint8_t* y, int64_t y_row_stride,
                             int batch, int h, int w, int nrow, int padding, int pad_value, int grid_h, int grid_w, gc_stream_t stream);
+
+/* ---- image projection: the noise regulariser and the noise normaliser (projection/, csrc/noise_reg.hip) ------------------------------------
+ * The reference's noise_regularize and noise_normalize_ (projection/projection.py:126-154) over a whole LIST of noise maps in a number of
+ * launches that depends neither on the length of the list nor on the depth of the pyramids (forward 3, backward 1, normalise 3).
+ *
+ * maps / grads: HOST arrays of n DEVICE pointers, map m a dense float32 [batches[m], 1, sizes[m], sizes[m]] (4-byte alignment is enough);
+ * sizes / batches / counts: HOST arrays.  sizes[m] is a power of two in [4, 1024]; n <= 32.  Pointers and extents travel by value in the
+ * kernel arguments: nothing is uploaded.
+ *
+ * gc_noise_reg_fwd_f32:  loss[0] (DEVICE) = sum over maps and pyramid levels of mean(n_l * roll(n_l, 1, x))^2 + mean(n_l * roll(n_l, 1, y))^2,
+ * the means over the whole tensor, batch included; n_0 = the map, n_(l+1) = the 2 x 2 means of n_l; the level loop is the reference's: the
+ * terms, stop if size <= 8, otherwise halve (a 4 x 4 and an 8 x 8 map contribute one level).  The workspace (gc_noise_reg_workspace bytes)
+ * receives the pyramids and the coefficients 2 * mean / N and must reach gc_noise_reg_bwd_f32 unchanged, together with unchanged maps.
+ * gc_noise_reg_bwd_f32:  grads[m][b,0,y,x] = gout[0] * d loss / d maps[m][b,0,y,x], gout a DEVICE scalar (no host synchronisation): a gather of
+ * sum_l 0.25^l * (cx_l * (n_l[Y, X-1] + n_l[Y, X+1]) + cy_l * (n_l[Y-1, X] + n_l[Y+1, X])) at (Y, X) = (y >> l, x >> l), indices wrapped.
+ * gc_noise_normalize_f32:  every map becomes (n - mean) / std IN PLACE, mean and the unbiased standard deviation over all counts[m] >= 2
+ * elements; the variance is centred per chunk of 4096 elements and the chunks merged in float64 (nothing is squared before its mean is taken
+ * off).  Workspace: gc_noise_normalize_workspace bytes.
+ * Every sum is store-and-add in an order fixed by the shapes (no float atomics): the same inputs give the same bits.  Null pointers, an empty
+ * list, a size that is no power of two >= 4 or a count below 2 return GC_ERR_BAD_ARG, more than 32 maps, a size above 1024 or more than 2^31
+ * elements GC_ERR_UNSUPPORTED, a short workspace GC_ERR_WORKSPACE; the workspace queries return 0 for such a list.  Nothing is launched then. */
+size_t gc_noise_reg_workspace(const int32_t* sizes, const int32_t* batches, int n);
+int gc_noise_reg_fwd_f32(const float* const* maps, const int32_t* sizes, const int32_t* batches, int n, float* loss,
+                         void* workspace, size_t workspace_bytes, gc_stream_t stream);
+int gc_noise_reg_bwd_f32(const float* const* maps, const int32_t* sizes, const int32_t* batches, int n, const float* gout,
+                         float* const* grads, const void* workspace, size_t workspace_bytes, gc_stream_t stream);
+size_t gc_noise_normalize_workspace(const int64_t* counts, int n);
+int gc_noise_normalize_f32(float* const* maps, const int64_t* counts, int n, void* workspace, size_t workspace_bytes, gc_stream_t stream);
 
 #ifdef __cplusplus
 }
