@@ -87,6 +87,15 @@ class ControllerTrainer:
         latent[:, lo:hi] = group_latent
         return latent
 
+    def save_nets(self, i, save_dir):
+        """``<save_dir>/checkpoint/<i:06d>.pt`` holding 'controller' (the FcStack's state_dict) and 'fc_optim': with
+        ``trainers.utils.save_args(config, save_dir)`` next to it, the directory inference.Controller loads for this group.  -> the path."""
+        import os
+        path = os.path.join(save_dir, 'checkpoint', '%s.pt' % str(i).zfill(6))
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        torch.save({'controller': self.fc_controller.state_dict(), 'fc_optim': self.fc_optim.state_dict()}, path)
+        return path
+
     @torch.no_grad()
     def generate(self, org_latent, controls):
         """Images of the frozen generator for latents whose group slice comes from the controller."""

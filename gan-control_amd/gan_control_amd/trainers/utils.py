@@ -115,3 +115,15 @@ def set_grad_none(model, targets):
     for name, param in named_params(model):
         if name in targets:
             param.grad = None
+
+
+def save_args(config, save_dir):
+    """``<save_dir>/args.json``: the configuration a run was started with (``model_config``, ``training_config``, ...), the file
+    inference.Inference and inference.Controller read next to ``checkpoint/``.  -> its path."""
+    import json
+    import os
+    os.makedirs(save_dir, exist_ok=True)
+    path = os.path.join(save_dir, 'args.json')
+    with open(path, 'w') as f:
+        json.dump(dict(config), f, indent=2, sort_keys=True)
+    return path

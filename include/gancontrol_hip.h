@@ -681,6 +681,29 @@ int gc_noise_reg_bwd_f32(const float* const* maps, const int32_t* sizes, const i
 size_t gc_noise_normalize_workspace(const int64_t* counts, int n);
 int gc_noise_normalize_f32(float* const* maps, const int64_t* counts, int n, void* workspace, size_t workspace_bytes, gc_stream_t stream);
 
+/* ---- whole EqualLinear stacks: the mapping networks and the controllers of the inference API (models/op/fc_stack.py, csrc/fc_stack.hip) -----
+ * n_stacks independent stacks of EqualLinear(activation='fused_lrelu') layers (gan_model.py:171-202, :25-41) on `batch` rows each, in one
+ * launch per 8 stacks: what Generator.style (MultiFcStack, gan_model.py:489-502: PixelNorm on the group's slice, gan_model.py:58-63) and the
+ * controllers' FcStack (controller_model.py:13-53) compute layer by layer.  Stack s:
+ *   h_0     = pixel_norm[s] ? x_s * rsqrt(mean_k(x_s^2) + 1e-8) : x_s                       (the mean over the stack's own in_dim[s] columns)
+ *   h_(l+1) = leaky_relu(alpha_l * h_l @ W_l^T + beta_l * bias_l, 0.2) * sqrt(2)            (alpha = lr_mul / sqrt(in), beta = lr_mul)
+ *   y_s[b, :] = h_(n_layers[s])[b, :]
+ * Per stack (HOST arrays of n_stacks entries): x[s] / y[s] DEVICE pointers, row b at x[s] + b * x_stride[s] and y[s] + b * y_stride[s]
+ * (strides in ELEMENTS, at least the row's width; any 4-byte alignment: a column slice of a wider [batch, 512] tensor is fine, which is
+ * how one call reads the groups of z, writes the groups of w without a cat, and splices a controller's output into w), in_dim[s],
+ * n_layers[s], pixel_norm[s].  Per layer (HOST arrays of sum_s n_layers[s] entries, stack after stack): w DEVICE [out_dim, in] dense, the
+ * parameter layout (in = the previous layer's out_dim, or in_dim[s]); bias DEVICE [out_dim] or NULL; out_dim; alpha; beta.  A layer whose
+ * `in` is a multiple of 4 and whose w is 16-byte aligned streams its rows with 16-byte loads, any other one with 4-byte loads.
+ * No y row may overlap an x row or a y row of another stack of the same call.  Only the out_dim columns of the `batch` rows of y are
+ * stored; no byte outside the in_dim columns of the `batch` rows of x, the weights and the biases is loaded.  fp32 FMA, every sum in an
+ * order fixed by the shapes: the same inputs give the same bits.  The tables travel by value in the kernel arguments: nothing is uploaded.
+ * Built: 1 .. 8 layers per stack, widths 1 .. 512, batch >= 1, any number of stacks; anything else returns GC_ERR_UNSUPPORTED (batch < 1
+ * included); null pointers, n_stacks < 0 and short strides GC_ERR_BAD_ARG.  Nothing is launched then.  n_stacks == 0 is a no-op. */
+int gc_fc_stacks_fwd_f32(const float* const* x, const int64_t* x_stride, float* const* y, const int64_t* y_stride,
+                         const int32_t* in_dim, const int32_t* n_layers, const int32_t* pixel_norm,
+                         const float* const* w, const float* const* bias, const int32_t* out_dim, const float* alpha, const float* beta,
+                         int n_stacks, int batch, gc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
