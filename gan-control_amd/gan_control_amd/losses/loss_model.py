@@ -14,6 +14,12 @@ The predictor networks themselves (ArcFace IR-SE50, Hopenet, ESR-9, DEX age, hai
 pretrained weights the reference downloads, README.md:97-108) are NOT part of this repository: pass any module / callable
 with the ``calc_features`` contract as ``skeleton_model``.  The distance functions of the reference's criteria are here
 (``CRITERIA``); they are a handful of elementwise / reduction ops on ``[mini_batch, ...]`` tensors.
+
+The evaluation half of the class (loss_model.py:204-321) is here as well: ``calc_distances_list`` / ``calc_distances`` /
+``calc_same_not_same_list``, ``L1Expend`` and ``get_same_not_same_list``, which the separability evaluation (evaluation/separability.py) runs
+on thousands of samples.  Their all-pairs distances and per-query minima are ``models.op.pairwise.pairwise_distances`` -- one HIP call on
+device features under that module's dispatch rule, the reference's chunked formula otherwise.  ``calc_mini_batch_loss`` does not use it: the
+mini-batch losses keep their autograd torch formulas.
 """
 import torch
 
@@ -143,3 +149,111 @@ class LossModelClass:
         emb = torch.cat([same[-1], other[-1]], dim=0)
         dist = self.last_layer_criterion(emb, emb)
         return loss + self.weights[-1] * self._level_loss(dist, masks, self.focus_on_list[-1], self.last_lower_thres, self.last_upper_thres)
+
+    # -- the evaluation half (loss_model.py:204-285): all-pairs distances of two feature sets and their same / not-same split ----------
+    def calc_distances_list(self, signatures_list, queries_list, last_layer_separability_only=False):
+        """One [signatures, queries] distance matrix per feature level (loss_model.py:238-250): intermediate levels under ``L1Expend`` -- or
+        under the last-layer criterion with ``intermediate_criterion_as_last_layer`` -- and skipped altogether when only the last layer is
+        wanted; the last level under ``last_layer_criterion``."""
+        as_last = bool(self.config.get('intermediate_criterion_as_last_layer'))
+        distances_list = []
+        for i, (signatures, queries) in enumerate(zip(signatures_list, queries_list)):
+            if i + 1 < len(signatures_list):
+                if last_layer_separability_only:
+                    continue
+                distances_list.append(self.calc_distances(signatures, queries, self.last_layer_criterion if as_last else L1Expend()))
+            else:
+                distances_list.append(self.calc_distances(signatures, queries, self.last_layer_criterion))
+        return distances_list
+
+    def calc_distances(self, signatures, queries, distance_fn, batch_size=20):
+        """``distance_fn`` over every (signature, query) pair -> a [signatures, queries] tensor on the features' device (the reference hands
+        back a numpy array, loss_model.py:252-285).  ``L1Expend`` and the criteria of ``CRITERIA`` on the row shapes they are written for are
+        the 'abs' / 'sq' modes of ``models.op.pairwise.pairwise_distances`` (one HIP call under its dispatch rule); any other callable -- and
+        a criterion on rows it does not reduce to a matrix -- is evaluated chunk pair by chunk pair, ``batch_size`` rows a side, and must
+        give a [chunk, chunk] matrix (ValueError otherwise).  No gradient is recorded, as in the reference."""
+        from ..models.op import pairwise
+        signatures, queries = _as_tensor(signatures), _as_tensor(queries)
+        mode = _mode_of(distance_fn, signatures)
+        with torch.no_grad():
+            if mode is not None:
+                return pairwise.pairwise_distances(signatures, queries, mode, batch_size=batch_size)
+            return pairwise.pairwise_distances(signatures, queries, None, criterion=distance_fn, batch_size=batch_size)
+
+    def calc_same_not_same_list(self, signatures_list, queries_list, signature_pids, queries_pids, last_layer_separability_only=False):
+        """Per level a dict of 'same' (distances of the pairs with equal pids), 'not_same' (per query the closest signature of ANOTHER pid:
+        the "2nd best"), 'all_not_same' and 'pids_2nd_best_pairs_df' (columns signature / queries / distance: the pid pair behind every
+        'not_same' entry), in the reference's order (loss_model.py:204-236): query-major, rows in order within a query.  The selections
+        are masked reads of the TRANSPOSED matrix and the minima come with the distances (pairwise_distances); there is no per-query loop.
+        Values are float32 numpy arrays; the frame is a pandas DataFrame built once from three arrays, or -- without pandas -- a dict of
+        them.  A query whose every signature shares its pid raises ValueError (the reference's np.min of an empty row does)."""
+        import numpy as np
+        from ..models.op import pairwise
+        n_levels = len(signatures_list)
+        levels = [n_levels - 1] if last_layer_separability_only else list(range(n_levels))
+        as_last = bool(self.config.get('intermediate_criterion_as_last_layer'))
+        signature_pids, queries_pids = np.asarray(signature_pids).reshape(-1), np.asarray(queries_pids).reshape(-1)
+        same_not_same_list = []
+        for level in levels:
+            signatures, queries = _as_tensor(signatures_list[level]), _as_tensor(queries_list[level])
+            fn = self.last_layer_criterion if (level == n_levels - 1 or as_last) else L1Expend()
+            mode = _mode_of(fn, signatures)
+            with torch.no_grad():
+                d, best, best_idx = pairwise.pairwise_distances(signatures, queries, mode, signature_pids, queries_pids,
+                                                                criterion=None if mode is not None else fn)
+                same_mask = torch.from_numpy(signature_pids[:, None] == queries_pids[None, :]).to(d.device)
+                by_query = d.t()
+                same = by_query[same_mask.t()].cpu().numpy()
+                all_not_same = by_query[~same_mask.t()].cpu().numpy()
+                not_same = best.cpu().numpy()
+                rows = best_idx.cpu().numpy()
+            same_not_same_list.append({'same': same, 'not_same': not_same, 'all_not_same': all_not_same,
+                                       'pids_2nd_best_pairs_df': _pairs_frame(signature_pids[rows], queries_pids, not_same)})
+        return same_not_same_list
+
+
+def _as_tensor(features):
+    return features if torch.is_tensor(features) else torch.as_tensor(features)
+
+
+def _pairs_frame(signature, queries, distance):
+    columns = {'signature': signature, 'queries': queries, 'distance': distance}
+    try:
+        import pandas as pd
+    except ImportError:
+        return columns
+    return pd.DataFrame(columns)
+
+
+class L1Expend(torch.nn.Module):
+    """Mean absolute difference of every (signature, query) pair over all trailing axes of [n, c, h, w] maps or [n, k] rows
+    (loss_model.py:308-321)."""
+
+    def __call__(self, signatures, queries):
+        if signatures.dim() not in (2, 4):
+            raise ValueError('L1Expend: [n, c, h, w] maps or [n, k] rows expected, got %s' % (tuple(signatures.shape),))
+        d = signatures.unsqueeze(1) - queries.unsqueeze(0)
+        return d.abs().mean(tuple(range(2, d.dim())))
+
+
+# criterion -> (mode of models.op.pairwise, the row ranks on which the criterion reduces every trailing axis): on any other rank the criterion
+# itself is called, and what it returns is checked (the squared-L2 criterion leaves [m, n, c, h] on 4-D maps)
+_KERNEL_FORMS = [(CRITERIA['embedding_loss'], 'sq', (2,)), (CRITERIA['dog_id_loss'], 'sq', (2,)), (CRITERIA['orientation_loss'], 'abs', (3,)),
+                 (CRITERIA['expression_loss'], 'abs', (3,)), (CRITERIA['age_loss'], 'abs', (2,))]
+
+
+def _mode_of(distance_fn, signatures):
+    if isinstance(distance_fn, L1Expend):
+        return 'abs' if signatures.dim() in (2, 4) else None
+    for fn, mode, ranks in _KERNEL_FORMS:
+        if distance_fn is fn:
+            return mode if signatures.dim() in ranks else None
+    return None
+
+
+def get_same_not_same_list(loss_model, features):
+    """Rows (2i, 2i + 1) of every level are one pid (loss_model.py:298-305): even rows are the signatures, odd rows the queries, read in
+    place (a row stride of two rows)."""
+    import numpy as np
+    pids = np.arange(0, len(features[0]), 2)
+    return loss_model.calc_same_not_same_list([f[::2] for f in features], [f[1::2] for f in features], pids, pids)

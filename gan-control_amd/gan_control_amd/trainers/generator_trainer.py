@@ -442,15 +442,17 @@ class GeneratorTrainer:
     # -- what a run shows for itself (init_evaluation :264-299, end_iter_update :721-733, save_images :774-850) ----------------------
     def make_tracker(self, inception=None, n_samples=16, seed=0):
         """The evaluation.Tracker of this run: ``n_samples`` fixed latents and injection noises on the host, drawn once from ``seed`` (the
-        reference draws them in its constructor, :65-75), ``inception`` for FID and ``config['evaluation_config']['fid']`` when there is one."""
+        reference draws them in its constructor, :65-75), ``inception`` for FID and the ``fid`` / ``separability`` sections of
+        ``config['evaluation_config']`` when there are any."""
         from ..evaluation.tracker import Tracker
         gen = torch.Generator().manual_seed(seed)
         latents = torch.randn(n_samples, self.model_config['latent_size'], generator=gen)
         noises = [torch.randn(n_samples, 1, 4, 4, generator=gen)]
         for i in range(3, self.generator.log_size + 1):
             noises += [torch.randn(n_samples, 1, 2 ** i, 2 ** i, generator=gen) for _ in range(2)]
-        fid_config = (self.config.get('evaluation_config') or {}).get('fid')
-        return Tracker(latents, noises, inception, self.model_config.get('g_noise_mode', 'normal'), fid_config=fid_config)
+        evaluation_config = self.config.get('evaluation_config') or {}
+        return Tracker(latents, noises, inception, self.model_config.get('g_noise_mode', 'normal'), fid_config=evaluation_config.get('fid'),
+                       separability_config=evaluation_config.get('separability'))
 
     def save_matrix(self, matrix_path, same_chunk_group, i, tracker, same_noise_for_all=False):
         size = self.model_config['size']
@@ -484,6 +486,14 @@ class GeneratorTrainer:
                                             same_noise_for_all=True))
         return written
 
+    def _same_chunks(self):
+        """{loss name: the ``place_in_latent`` columns of its ``same_group_name``} for the losses of this run (what the separability evaluation
+        makes pairs share); empty without sub-latent groups."""
+        if self.batch_utils is None:
+            return {}
+        return {name: self.batch_utils.place_in_latent_dict[self.training_config[name]['same_group_name']] for name in self.loss_models
+                if (self.training_config.get(name) or {}).get('same_group_name') in self.batch_utils.place_in_latent_dict}
+
     def _end_iter_evaluation(self, i, save_dir, tracker):
         """evaluate and save_images of end_iter_update (:724-727) on rank 0; an interval that is missing or 0 never fires."""
         if self.rank != 0:
@@ -492,7 +502,9 @@ class GeneratorTrainer:
         debug = tc.get('debug', False)
         every = tc.get('min_evaluate_interval', 0)
         if (every and i % every == 0) or (debug and i % 10 == 0):
-            tracker.evaluate(i, self.g_ema, debug=debug, graph_save_path=None if save_dir is None else os.path.join(save_dir, 'graphs'))
+            tracker.evaluate(i, self.g_ema, debug=debug, graph_save_path=None if save_dir is None else os.path.join(save_dir, 'graphs'),
+                             buckets_save_path=None if save_dir is None else os.path.join(save_dir, 'buckets'),
+                             loss_models=self.loss_models, same_chunks=self._same_chunks())
         every = tc.get('save_images_interval', 0)
         if save_dir is not None and ((every and i % every == 0) or (debug and i % 100 == 0)):
             self.save_images(i, save_dir, tracker)
@@ -502,8 +514,8 @@ class GeneratorTrainer:
         generator_update(i), then the checkpoint cadence of end_iter_update (:728-731: ``i % save_nets_interval == 0``).  ``data`` is an iterator
         of real batches already on the device (this rank's shard; None = a resident synthetic batch, what bench.py times).  With a ``tracker``
         (make_tracker) every iteration ends with the rest of end_iter_update's cadence on rank 0: ``min_evaluate_interval`` -> tracker.evaluate
-        (FID), ``save_images_interval`` -> save_images, and ``best_fid.pt`` next to a periodic checkpoint when FID is enabled and the last FID is
-        the best so far.  Tensorboard and the CSV monitor are left to ``on_iteration(i, trainer)``.  Returns the iteration counter after the
+        (FID, and separability on this run's loss models under ``<save_dir>/graphs`` and ``<save_dir>/buckets``), ``save_images_interval`` ->
+        save_images, and ``best_fid.pt`` next to a periodic checkpoint when FID is enabled and the last FID is the best so far.  Tensorboard and the CSV monitor are left to ``on_iteration(i, trainer)``.  Returns the iteration counter after the
         last step."""
         tc = self.training_config
         iters = tc.get('iter', 0) if iters is None else iters

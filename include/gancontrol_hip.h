@@ -704,6 +704,31 @@ int gc_fc_stacks_fwd_f32(const float* const* x, const int64_t* x_stride, float* 
                          const float* const* w, const float* const* bias, const int32_t* out_dim, const float* alpha, const float* beta,
                          int n_stacks, int batch, gc_stream_t stream);
 
+/* ---- all-pairs feature distances of the separability evaluation (models/op/pairwise.py, csrc/pairwise.hip) -----------------------------
+ * What LossModelClass.calc_distances computes chunk pair by chunk pair (loss_model.py:252-285) and the per-query minimum of
+ * calc_same_not_same_list (loss_model.py:214-229), in one call.  s [m, k] (signatures) and q [n, k] (queries): row i at s + i * s_stride,
+ * row j at q + j * q_stride (strides in ELEMENTS, at least k; elements of a row adjacent; any 4-byte alignment: features[::2] is read in
+ * place with stride 2 k).  d [m, n] dense:
+ *   GC_PAIRWISE_ABS: d[i, j] = (sum_c |s[i, c] - q[j, c]|) / k        (L1Expend, loss_model.py:308-321; the mean-absolute criteria)
+ *   GC_PAIRWISE_SQ:  d[i, j] = sum_c (s[i, c] - q[j, c])^2            (arc_face_criterion.py:15-21; the difference itself, no expansion)
+ * With s_pid [m] and q_pid [n] (DEVICE int32, both or neither) also, for every column j over the rows i with s_pid[i] != q_pid[j]:
+ * best[j] = min d[i, j] and best_idx[j] = the lowest such i that attains it -- taken over the float32 values stored in d, so min / argmin
+ * of the returned matrix reproduce them exactly (a column without such a row: +inf and -1).  Inputs are assumed finite.
+ * A tile kernel (operands staged through LDS, a register micro-tile per thread; 16-byte loads when both bases are 16-byte aligned and both
+ * strides and k are multiples of 4, else 4-byte loads) and, where long rows are split along k over workgroups or pids are given, a second
+ * launch that adds the partial sums of the workspace in ascending order, divides, stores d and takes the minima: at most two launches, no
+ * atomics, every sum in an order fixed by (m, n, k) -- the same inputs give the same bits.  Only d, best, best_idx and the workspace are
+ * stored; no byte outside the k columns of the m / n rows and the pids is loaded.  Workspace: gc_pairwise_workspace(m, n, k) bytes (0
+ * where nothing is split, and for extents below 1).  Null s / q / d, extents below 1, a stride below k, an unknown mode, one pid array
+ * without the other and pids without best / best_idx return GC_ERR_BAD_ARG, a short workspace GC_ERR_WORKSPACE, more than 65535 * 64 rows
+ * GC_ERR_UNSUPPORTED.  Nothing is launched then. */
+#define GC_PAIRWISE_ABS 0
+#define GC_PAIRWISE_SQ 1
+size_t gc_pairwise_workspace(int m, int n, int k);
+int gc_pairwise_f32(const float* s, int64_t s_stride, const float* q, int64_t q_stride, int m, int n, int k, int mode, float* d,
+                    const int32_t* s_pid, const int32_t* q_pid, float* best, int32_t* best_idx, void* workspace, size_t workspace_bytes,
+                    gc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
