@@ -607,38 +607,26 @@ __global__ __launch_bounds__(256) void wgrad_contract_cols_kernel(const float* _
 }
 
 // --------------------------------------------------------------------------------------------
-template <int WG_OC, int WG_PX, int KSPLIT, int KCT, int WOC, int WPX, int TPW, int UP, int DOWN, int KS>
-int launch_conv(ConvArgs a, hipStream_t s) {
-    using C = ConvCfg<WG_OC, WG_PX, KSPLIT, KCT, WOC, WPX, TPW, UP, DOWN, KS>;
-    const int qh = gc::ceil_div(a.out_h, UP), qw = gc::ceil_div(a.out_w, UP);
-    a.tiles_y = gc::ceil_div(qh, C::TPH);
-    a.tiles_x = gc::ceil_div(qw, TPW);
-    const long long gx = (long long)a.tiles_x * a.tiles_y * UP * UP * a.B;
-    if (gx > 2147483647LL) return gc::fail(GC_ERR_UNSUPPORTED, "gc_conv2d_f32: grid too large");
-    const int slices = a.k_per_split ? gc::ceil_div(a.K, a.k_per_split) : 1;
-    if (gc::probing()) return gc::probe_name("conv_mfma_kernel<%d,%d,%d,%d,%d,%d,%d>|up%d,down%d,k%d", WG_OC, WG_PX, KSPLIT, KCT, WOC, WPX, TPW, UP, DOWN, KS);
-    dim3 grid((unsigned)gx, gc::ceil_div(a.N, C::OCT), slices);
-    hipLaunchKernelGGL((conv_mfma_kernel<WG_OC, WG_PX, KSPLIT, KCT, WOC, WPX, TPW, UP, DOWN, KS>), grid, dim3(256), 0, s, a);
-    return gc::check_launch("gc_conv2d_f32");
-}
+// The decision of ONE fp32 forward launch, taken once by plan_f32 and read by the workspace query, the probe name and the launch.
+struct F32Plan {
+    bool small = false;                  // conv_f32_small_kernel<k, t0, t1, down, up>; else conv_mfma_kernel<t0 .. t6, up, down, k>
+    int t[7] = {0, 0, 0, 0, 0, 0, 0};
+    int (*launch)(const F32Plan&, const ConvArgs&, float*, hipStream_t) = nullptr;      // the launcher of that instance (part: the partial sums of a split launch)
+    int oct = 1, tiles_x = 0, tiles_y = 0;      // conv_mfma_kernel: output channels per workgroup and pixel tiles per phase sub-grid, from the instance's ConvCfg
+    long long gx = 0;                    // ... and grid x
+    int bgroup = 0;                      // small-plane kernel: samples per workgroup
+    size_t lds = 0;                      // ... and its dynamic LDS
+    int slices = 1, k_per_split = 0;     // slices over the input channels (small planes: one per workgroup row, always)
+    size_t need = 0;                     // bytes of partial sums the shape asks for (gc_conv2d_f32_workspace)
+    bool split = false;                  // THIS launch writes partial sums and runs the finish pass: the caller brought `need` bytes
+};
 
-// Planes up to 16 pixels wide (the 4x4 .. 16x16 layers, 512 channels): a launch has only B * N / 32 workgroups, each
-// walking all of K chunk by chunk with nothing to hide the load latency behind -- 70..120 us for a few GFLOP.  Splitting K
-// over blockIdx.z fills the chip and shortens the dependent chain; the slices are summed in a fixed order by
-// splitk_finish_kernel, which also applies out_scale and the fused epilogue.
-struct SplitPlan { int slices, k_per_split; };
-SplitPlan plan_splitk(const gc_conv_desc* d) {
-    SplitPlan sp{1, 0};
-    const int qw = gc::ceil_div(d->out_w, d->up), qh = gc::ceil_div(d->out_h, d->up);
-    if (qw > 16 || d->in_ch < 128) return sp;
-    const int tpw = qw <= 4 ? 4 : (qw <= 8 ? 8 : 16), rows = 32 / tpw;
-    const long long wgs = (long long)gc::ceil_div(qw, tpw) * gc::ceil_div(qh, rows) * d->up * d->up * d->batch * gc::ceil_div(d->out_ch, 32);
-    int want = (int)std::min<long long>(std::max<long long>(512 / std::max<long long>(wgs, 1), 1), d->in_ch / 64);
-    if (want <= 1) return sp;
-    sp.k_per_split = gc::ceil_div(gc::ceil_div(d->in_ch, want), 32) * 32;
-    sp.slices = gc::ceil_div(d->in_ch, sp.k_per_split);
-    if (sp.slices <= 1) { sp.slices = 1; sp.k_per_split = 0; }
-    return sp;
+template <int WG_OC, int WG_PX, int KSPLIT, int KCT, int WOC, int WPX, int TPW, class G>
+int launch_conv(const F32Plan& p, const ConvArgs& a, float*, hipStream_t s) {
+    using C = ConvCfg<WG_OC, WG_PX, KSPLIT, KCT, WOC, WPX, TPW, G::UP, G::DOWN, G::KS>;
+    dim3 grid((unsigned)p.gx, gc::ceil_div(a.N, C::OCT), p.split ? p.slices : 1);
+    hipLaunchKernelGGL((conv_mfma_kernel<WG_OC, WG_PX, KSPLIT, KCT, WOC, WPX, TPW, G::UP, G::DOWN, G::KS>), grid, dim3(256), 0, s, a);
+    return gc::check_launch("gc_conv2d_f32");
 }
 
 __global__ __launch_bounds__(256) void splitk_finish_kernel(ConvArgs p, int slices, long long per_slice) {
@@ -663,23 +651,55 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(ConvArgs p, int slic
     }
 }
 
-// tile configuration: by phase sub-grid width, output channels and how many workgroups result
-template <int UP, int DOWN, int KS>
-int dispatch_conv(const ConvArgs& a, hipStream_t s) {
-    const int qw = gc::ceil_div(a.out_w, UP), qh = gc::ceil_div(a.out_h, UP);
-    if (qw <= 4) return launch_conv<1, 1, 4, 32, 1, 1, 4, UP, DOWN, KS>(a, s);
-    if (qw <= 8) return launch_conv<1, 1, 4, 32, 1, 1, 8, UP, DOWN, KS>(a, s);
-    if (qw <= 16) return launch_conv<1, 1, 4, 32, 1, 1, 16, UP, DOWN, KS>(a, s);
+template <int WG_OC, int WG_PX, int KSPLIT, int KCT, int WOC, int WPX, int TPW, class G>
+void set_mfma(const gc_conv_desc* d, F32Plan& p) {
+    using C = ConvCfg<WG_OC, WG_PX, KSPLIT, KCT, WOC, WPX, TPW, G::UP, G::DOWN, G::KS>;
+    const int t[7] = {WG_OC, WG_PX, KSPLIT, KCT, WOC, WPX, TPW};
+    std::copy(t, t + 7, p.t);
+    p.launch = &launch_conv<WG_OC, WG_PX, KSPLIT, KCT, WOC, WPX, TPW, G>;
+    p.oct = C::OCT;
+    p.tiles_y = gc::ceil_div(gc::ceil_div(d->out_h, G::UP), C::TPH);
+    p.tiles_x = gc::ceil_div(gc::ceil_div(d->out_w, G::UP), TPW);
+    p.gx = (long long)p.tiles_x * p.tiles_y * G::UP * G::UP * d->batch;
+}
+
+// conv_mfma_kernel.  Tile configuration (plan_mfma_tile): by phase sub-grid width, output channels and how many workgroups result.  Split (plan_mfma):
+// planes up to 16 pixels wide (the 4x4 .. 16x16 layers, 512 channels): a launch has only B * N / 32 workgroups, each
+// walking all of K chunk by chunk with nothing to hide the load latency behind -- 70..120 us for a few GFLOP.  Splitting K
+// over blockIdx.z fills the chip and shortens the dependent chain; the slices are summed in a fixed order by
+// splitk_finish_kernel, which also applies out_scale and the fused epilogue.
+template <class G>
+void plan_mfma_tile(const gc_conv_desc* d, F32Plan& p) {
+    constexpr int UP = G::UP, DOWN = G::DOWN, KS = G::KS;
+    const int qw = gc::ceil_div(d->out_w, UP), qh = gc::ceil_div(d->out_h, UP), N = d->out_ch;
+    if (qw <= 4) return set_mfma<1, 1, 4, 32, 1, 1, 4, G>(d, p);
+    if (qw <= 8) return set_mfma<1, 1, 4, 32, 1, 1, 8, G>(d, p);
+    if (qw <= 16) return set_mfma<1, 1, 4, 32, 1, 1, 16, G>(d, p);
     if constexpr (DOWN == 2) {
-        if (a.N <= 64) return launch_conv<2, 2, 1, 8, 1, 1, 32, UP, DOWN, KS>(a, s);
+        if (N <= 64) return set_mfma<2, 2, 1, 8, 1, 1, 32, G>(d, p);
     } else {
-        if (a.N <= 32) return launch_conv<1, 4, 1, 8, 1, 4, 32, UP, DOWN, KS>(a, s);
-        if (a.N <= 64) return launch_conv<1, 4, 1, 8, 2, 2, 32, UP, DOWN, KS>(a, s);
+        if (N <= 32) return set_mfma<1, 4, 1, 8, 1, 4, 32, G>(d, p);
+        if (N <= 64) return set_mfma<1, 4, 1, 8, 2, 2, 32, G>(d, p);
     }
     // 128oc x (4 rows x 32 px) tiles unless that leaves most CUs idle
-    const long long big = (long long)gc::ceil_div(qw, 32) * gc::ceil_div(qh, 4) * UP * UP * a.B * gc::ceil_div(a.N, 128);
-    if (big < 512) return launch_conv<2, 2, 1, 8, 1, 1, 32, UP, DOWN, KS>(a, s);
-    return launch_conv<2, 2, 1, 8, 2, 2, 32, UP, DOWN, KS>(a, s);
+    using Big = ConvCfg<2, 2, 1, 8, 2, 2, 32, UP, DOWN, KS>;
+    const long long big = (long long)gc::ceil_div(qw, 32) * gc::ceil_div(qh, Big::TPH) * UP * UP * d->batch * gc::ceil_div(N, Big::OCT);
+    if (big < 512) return set_mfma<2, 2, 1, 8, 1, 1, 32, G>(d, p);
+    return set_mfma<2, 2, 1, 8, 2, 2, 32, G>(d, p);
+}
+
+template <class G>
+void plan_mfma(const gc_conv_desc* d, F32Plan& p) {
+    plan_mfma_tile<G>(d, p);
+    if (gc::ceil_div(d->out_w, G::UP) > 16 || d->in_ch < 128) return;
+    const int N = d->out_ch;
+    const long long wgs = p.gx * gc::ceil_div(N, p.oct);
+    const int want = (int)std::min<long long>(std::max<long long>(512 / std::max<long long>(wgs, 1), 1), d->in_ch / 64);
+    if (want <= 1) return;
+    const int kps = gc::ceil_div(gc::ceil_div(d->in_ch, want), 32) * 32, slices = gc::ceil_div(d->in_ch, kps);
+    if (slices <= 1) return;
+    p.slices = slices;
+    p.k_per_split = kps;
 }
 
 struct WgradPlan { int cfg, kt, nt, tr, splits, tiles_per_split, tiles_x, tiles_y, parts; };
@@ -840,9 +860,9 @@ inline int small_bgroup(const gc_conv_desc* d) {
 }
 
 // shapes the small-plane kernel takes: 1x1 / 3x3 taps at stride 1 with "same" padding or at stride 2 without padding, output planes <= 8 x 8;
-// 3x3 taps with up = 2 onto planes <= 10 x 10 (4^2 -> 9^2); >= 64 input and output channels (any count), dense rows, and a patch that fits the
-// LDS next to the weight slab (many samples of tiny planes are split into sample groups: their halo is most of the patch)
-inline bool small_eligible(const gc_conv_desc* d) {
+// 3x3 taps with up = 2 onto planes <= 10 x 10 (4^2 -> 9^2); >= 64 input and output channels (any count), dense rows -- and (plan_small) a patch that
+// fits the LDS next to the weight slab (many samples of tiny planes are split into sample groups: their halo is most of the patch)
+inline bool small_shape(const gc_conv_desc* d) {
 #ifdef GC_NO_SMALL
     return false;
 #endif
@@ -859,36 +879,42 @@ inline bool small_eligible(const gc_conv_desc* d) {
         if (d->out_w > 8 || d->out_h > 8) return false;
     } else return false;
     if ((d->in_pitch != 0 && d->in_pitch != d->in_w) || !dense_output(d)) return false;
-    if (d->in_ch < 64 || d->out_ch < 64) return false;
-    return small_bgroup(d) >= 1;
+    return d->in_ch >= 64 && d->out_ch >= 64;
 }
 
-// channel chunks per workgroup: two (32 channels x 32 output channels) when the partial sums of 16-channel slices would outweigh the weights
-inline int small_chunks(const gc_conv_desc* d) {
-    const int bg = small_bgroup(d);
-    if (d->in_ch % (2 * SMALL_KC) != 0 || small_lds_bytes(d, 2, bg) > small_lds_max()) return 1;
-#ifdef GC_SMALL_NCH
-    return GC_SMALL_NCH;
-#endif
-    const long long pixels = (long long)d->batch * d->out_h * d->out_w;
-    return pixels > 16 * d->kh * d->kw ? 2 : 1;     // slices * pixels * N * 4 bytes  vs  taps * K * N * 4 bytes
-}
-inline int small_slices(const gc_conv_desc* d) { return gc::ceil_div(d->in_ch, SMALL_KC * small_chunks(d)); }
-
-template <int KS, int DOWN, int UP = 1>
-int launch_small(const gc_conv_desc* d, const SmallArgs& sa, hipStream_t s) {
-    const size_t lds = small_lds_bytes(d, small_chunks(d), sa.bgroup);
-    const unsigned groups = (unsigned)gc::ceil_div(d->batch, sa.bgroup);
-    if (small_chunks(d) == 2) {
-        static bool done[16] = {false};
-        if (int rc = gc::allow_dynamic_lds(reinterpret_cast<const void*>(&conv_f32_small_kernel<KS, 1, 2, DOWN, UP>), small_lds_max(), done, "gc_conv2d_f32(small planes)")) return rc;
-        hipLaunchKernelGGL((conv_f32_small_kernel<KS, 1, 2, DOWN, UP>), dim3(small_slices(d), gc::ceil_div(d->out_ch, 32), groups), dim3(SMALL_THREADS), lds, s, sa);
-    } else {
-        static bool done[16] = {false};
-        if (int rc = gc::allow_dynamic_lds(reinterpret_cast<const void*>(&conv_f32_small_kernel<KS, 2, 1, DOWN, UP>), small_lds_max(), done, "gc_conv2d_f32(small planes)")) return rc;
-        hipLaunchKernelGGL((conv_f32_small_kernel<KS, 2, 1, DOWN, UP>), dim3(small_slices(d), gc::ceil_div(d->out_ch, 64), groups), dim3(SMALL_THREADS), lds, s, sa);
-    }
+template <int KS, int WOC, int NCH, int DOWN, int UP>
+int launch_small(const F32Plan& p, const ConvArgs& a, float* part, hipStream_t s) {
+    const SmallArgs sa{a, part, (long long)a.B * a.N * a.out_h * a.out_w, p.bgroup};
+    static bool done[16] = {false};
+    if (int rc = gc::allow_dynamic_lds(reinterpret_cast<const void*>(&conv_f32_small_kernel<KS, WOC, NCH, DOWN, UP>), small_lds_max(), done, "gc_conv2d_f32(small planes)")) return rc;
+    const dim3 grid(p.slices, gc::ceil_div(a.N, 32 * WOC), (unsigned)gc::ceil_div(a.B, p.bgroup));
+    hipLaunchKernelGGL((conv_f32_small_kernel<KS, WOC, NCH, DOWN, UP>), grid, dim3(SMALL_THREADS), p.lds, s, sa);
     return gc::check_launch("gc_conv2d_f32(small planes)");
+}
+
+// The small-plane kernel's plan for a shape of small_shape(); false when not even one sample fits the LDS.
+template <int KS, int DOWN, int UP>
+bool plan_small(const gc_conv_desc* d, F32Plan& p) {
+    const int bg = small_bgroup(d);
+    if (bg < 1) return false;
+    // channel chunks per workgroup: two (32 channels x 32 output channels) when the partial sums of 16-channel slices would outweigh the weights
+    int nch = 1;
+    if (d->in_ch % (2 * SMALL_KC) == 0 && small_lds_bytes(d, 2, bg) <= small_lds_max()) {
+#ifdef GC_SMALL_NCH
+        nch = GC_SMALL_NCH;
+#else
+        nch = (long long)d->batch * d->out_h * d->out_w > 16 * d->kh * d->kw ? 2 : 1;     // slices * pixels * N * 4 bytes  vs  taps * K * N * 4 bytes
+#endif
+    }
+    p.small = true;
+    p.t[0] = nch == 2 ? 1 : 2;
+    p.t[1] = nch;
+    if (nch == 2) p.launch = &launch_small<KS, 1, 2, DOWN, UP>;
+    else          p.launch = &launch_small<KS, 2, 1, DOWN, UP>;
+    p.bgroup = bg;
+    p.lds = small_lds_bytes(d, nch, bg);
+    p.slices = gc::ceil_div(d->in_ch, SMALL_KC * nch);      // one slice per workgroup row
+    return true;
 }
 
 // --------------------------------------------------------------------------------------------
@@ -1049,6 +1075,36 @@ int dispatch_wgrad(const WgradArgs& a, const WgradPlan& pl, hipStream_t s) {
     return gc::check_launch("gc_conv2d_wgrad_f32(mfma)");
 }
 
+// THE decision of an fp32 forward launch (the thin 1x1 shapes of pointwise.hip aside).  room: the bytes of workspace the caller brought.
+F32Plan plan_f32(const gc_conv_desc* d, size_t room) {
+    F32Plan p;
+    const size_t per_slice = (size_t)d->batch * d->out_ch * d->out_h * d->out_w * sizeof(float);
+    if (small_shape(d)) {
+        if (d->up == 2)        plan_small<3, 1, 2>(d, p);
+        else if (d->down == 2) d->kh == 3 ? plan_small<3, 2, 1>(d, p) : plan_small<1, 2, 1>(d, p);
+        else                   d->kh == 3 ? plan_small<3, 1, 1>(d, p) : plan_small<1, 1, 1>(d, p);
+    }
+    if (p.small) {
+        p.need = p.slices * per_slice;
+        p.split = true;
+        if (gc::probing() || room >= p.need) return p;      // (the probe names this kernel although it brings no workspace)
+        // without room for its slices the shape runs unsplit on conv_mfma_kernel
+        const size_t need = p.need;
+        p = F32Plan();
+        p.need = need;
+    }
+    with_geom(d, [&](auto g) { plan_mfma<decltype(g)>(d, p); });
+    if (p.need == 0 && p.slices > 1) p.need = p.slices * per_slice;
+    p.split = p.slices > 1 && room >= p.need;
+    return p;
+}
+
+int probe_f32(const gc_conv_desc* d, const F32Plan& p) {
+    const int* t = p.t;
+    if (p.small) return gc::probe_name("conv_f32_small_kernel<%d,%d,%d,%d>|up%d,down%d,k%d", d->kh, t[0], t[1], d->down, d->up, d->down, d->kh);
+    return gc::probe_name("conv_mfma_kernel<%d,%d,%d,%d,%d,%d,%d>|up%d,down%d,k%d", t[0], t[1], t[2], t[3], t[4], t[5], t[6], d->up, d->down, d->kh);
+}
+
 }  // namespace
 
 // 3 x 3 weight gradients the small-plane kernel takes: stride 1 with "same" padding or stride 2 without padding onto planes <= 8 x 8, dense rows,
@@ -1072,9 +1128,7 @@ bool gcconv::wgrad_small_eligible(const gc_conv_desc* d) {
 
 size_t gcconv::conv2d_f32_workspace(const gc_conv_desc* d) {
     if (!d || d->batch <= 0 || d->in_ch <= 0 || d->out_ch <= 0 || d->out_h <= 0 || d->out_w <= 0 || d->up <= 0) return 0;
-    if (small_eligible(d)) return (size_t)small_slices(d) * d->batch * d->out_ch * d->out_h * d->out_w * sizeof(float);      // one slice per workgroup row
-    const SplitPlan sp = plan_splitk(d);
-    return sp.slices > 1 ? (size_t)sp.slices * d->batch * d->out_ch * d->out_h * d->out_w * sizeof(float) : 0;
+    return plan_f32(d, 0).need;
 }
 
 int gcconv::conv2d_f32_ws(const gc_conv_desc* d, const float* x, const float* w, const float* in_scale, const float* out_scale,
@@ -1087,42 +1141,29 @@ int gcconv::conv2d_f32_ws(const gc_conv_desc* d, const float* x, const float* w,
     if ((rc = validate_epilogue(ep, "gc_conv2d_f32"))) return rc;
     if (d->batch == 0) return GC_OK;
     if (pointwise_thin(d)) return pointwise_conv(d, x, w, in_scale, out_scale, ep, y, stream);
+    const F32Plan p = plan_f32(d, workspace ? workspace_bytes : 0);
+    if (!p.small && p.gx > 2147483647LL) return gc::fail(GC_ERR_UNSUPPORTED, "gc_conv2d_f32: grid too large");
+    if (gc::probing()) return probe_f32(d, p);
     ConvArgs a{x, w, in_scale, out_scale, y, d->batch, d->in_ch, d->out_ch, d->in_h, d->in_w, d->out_h, d->out_w,
                d->pad_y, d->pad_x, 0, 0};
     set_epilogue(a, ep);
     a.k_per_split = 0; a.part = nullptr;
     hipStream_t s = (hipStream_t)stream;
-    const size_t need = conv2d_f32_workspace(d);
-    if (small_eligible(d) && (gc::probing() || (workspace && workspace_bytes >= need))) {
-        if (gc::probing()) return gc::probe_name("conv_f32_small_kernel<%d,%d,%d,%d>|up%d,down%d,k%d", d->kh, small_chunks(d) == 2 ? 1 : 2, small_chunks(d), d->down, d->up, d->down, d->kh);
-        SmallArgs sa{a, static_cast<float*>(workspace), (long long)d->batch * d->out_ch * d->out_h * d->out_w, small_bgroup(d)};
-        if (d->up == 2)        rc = launch_small<3, 1, 2>(d, sa, s);
-        else if (d->down == 2) rc = d->kh == 3 ? launch_small<3, 2>(d, sa, s) : launch_small<1, 2>(d, sa, s);
-        else                   rc = d->kh == 3 ? launch_small<3, 1>(d, sa, s) : launch_small<1, 1>(d, sa, s);
-        if (rc) return rc;
-        ConvArgs fin_s = a;
-        fin_s.part = sa.part;
-        return launch_splitk_finish(fin_s, small_slices(d), sa.per_slice, s);
-    }
-    const SplitPlan sp = plan_splitk(d);
-    const bool split = sp.slices > 1 && workspace && workspace_bytes >= need;
-    ConvArgs fin = a;
-    if (split) {        // raw partial sums now, out_scale + epilogue in the finish pass
+    const ConvArgs fin = a;
+    float* part = p.split ? static_cast<float*>(workspace) : nullptr;
+    a.tiles_x = p.tiles_x;
+    a.tiles_y = p.tiles_y;
+    if (p.split && !p.small) {        // raw partial sums now, out_scale + epilogue in the finish pass (the small-plane kernel writes nothing else)
         a.so = nullptr;
         set_epilogue(a, nullptr);
-        a.k_per_split = sp.k_per_split;
-        a.part = static_cast<float*>(workspace);
+        a.k_per_split = p.k_per_split;
+        a.part = part;
     }
-    if (d->kh == 3) {
-        if (d->up == 2) rc = dispatch_conv<2, 1, 3>(a, s);
-        else rc = d->down == 2 ? dispatch_conv<1, 2, 3>(a, s) : dispatch_conv<1, 1, 3>(a, s);
-    } else {
-        if (d->up == 2) rc = dispatch_conv<2, 1, 1>(a, s);
-        else rc = d->down == 2 ? dispatch_conv<1, 2, 1>(a, s) : dispatch_conv<1, 1, 1>(a, s);
-    }
-    if (rc || !split) return rc;
-    fin.part = static_cast<float*>(workspace);
-    return launch_splitk_finish(fin, sp.slices, (long long)d->batch * d->out_ch * d->out_h * d->out_w, s);
+    rc = p.launch(p, a, part, s);
+    if (rc || !p.split) return rc;
+    ConvArgs fin_p = fin;
+    fin_p.part = part;
+    return launch_splitk_finish(fin_p, p.slices, (long long)d->batch * d->out_ch * d->out_h * d->out_w, s);
 }
 
 int gcconv::launch_splitk_finish(const ConvArgs& fin, int slices, long long per_slice, hipStream_t s) {

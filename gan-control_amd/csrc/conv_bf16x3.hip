@@ -17,7 +17,7 @@
 // Register-prefetch pipeline over chunks, compile-time geometry, phase decomposition for up = 2.
 //
 // This unit: the weight pack, conv_bf16x3_kernel (every role in every wave), conv_bf16x3_ws_kernel (wave-specialised, the wide stride-1
-// layers), their launchers, the dispatcher, the split-K planner, the forward entry points and the shape queries.  The transposed
+// layers), their launchers, the plan of a forward launch (plan_conv), the forward entry points and the shape queries.  The transposed
 // convolution is convt_bf16x3.hip, the weight gradient wgrad_bf16x3.hip, the wave-specialised stride-2 kernel conv_s2ws.hip.
 #include "conv_common.h"
 #include "conv_bf16x3_shared.h"
@@ -787,101 +787,135 @@ __global__ __launch_bounds__(768) void conv_bf16x3_ws_kernel(Bf16Args a) {
 }
 
 
-template <int WG_OC, int WG_PX, int WOC, int WPX, int UP, int DOWN, int KS>
-int launch(Bf16Args a, hipStream_t s) {
-    using C = BCfg<WG_OC, WG_PX, WOC, WPX, UP, DOWN, KS>;
-    const int qh = gc::ceil_div(a.c.out_h, UP), qw = gc::ceil_div(a.c.out_w, UP);
-    a.c.tiles_y = gc::ceil_div(qh, C::TPH);
-    a.c.tiles_x = gc::ceil_div(qw, 32);
-    const int tiles = a.c.tiles_x * a.c.tiles_y, ocb = gc::ceil_div(a.c.N, C::OCT);
-    // tiles per workgroup: as many as keep >= 8 workgroups per CU-slot pair (2048 on 256 CUs x 2) in the launch, at most 8;
-    // few channel chunks per tile is where the per-tile latencies dominate, many chunks need no help
-    a.tpb = 1;
-    if (UP == 1) {
-        const long long wgs = (long long)tiles * a.c.B * ocb;
-        const int nchunks = gc::ceil_div(a.c.K, KCB);
-        int want = nchunks <= 2 ? 8 : (nchunks <= 4 ? 4 : (nchunks <= 8 ? 2 : 1));
-        while (want > 1 && wgs / want < 2048) want >>= 1;
-        a.tpb = want;
-    }
-    if (a.k_per_split) a.tpb = 1;
-    a.groups = gc::ceil_div(tiles, a.tpb);
-    const long long gx = (long long)a.groups * UP * UP * a.c.B;
-    if (gx > 2147483647LL) return gc::fail(GC_ERR_UNSUPPORTED, "gc_conv2d_bf16x3_f32: grid too large");
-    if (gc::probing()) return gc::probe_name("conv_bf16x3_kernel<%d,%d,%d,%d>|up%d,down%d,k%d", WG_OC, WG_PX, WOC, WPX, UP, DOWN, KS);
-    dim3 grid((unsigned)gx, ocb, a.k_per_split ? gc::ceil_div(a.c.K, a.k_per_split) : 1);
-    hipLaunchKernelGGL((conv_bf16x3_kernel<WG_OC, WG_PX, WOC, WPX, UP, DOWN, KS>), grid, dim3(256), 0, s, a);
+// ---- the launchers: each instantiates what the plan says (tiling, grid and split are the plan's) ----
+
+template <int WOC, int WPX, class G>
+int launch(const ConvPlan& p, const Bf16Args& a, hipStream_t s) {
+    using C = BCfg<1, 4, WOC, WPX, G::UP, G::DOWN, G::KS>;
+    dim3 grid((unsigned)p.gx, gc::ceil_div(a.c.N, C::OCT), p.split ? p.slices : 1);
+    hipLaunchKernelGGL((conv_bf16x3_kernel<1, 4, WOC, WPX, G::UP, G::DOWN, G::KS>), grid, dim3(256), 0, s, a);
     return gc::check_launch("gc_conv2d_bf16x3_f32");
+}
+
+template <class G>
+int launch_one_role(const ConvPlan& p, const Bf16Args& a, hipStream_t s) {
+    const int woc = p.t[2], wpx = p.t[3];
+    if constexpr (G::DOWN == 2) return woc == 1 ? launch<1, 1, G>(p, a, s) : launch<2, 1, G>(p, a, s);
+    else return woc == 1 ? launch<1, 2, G>(p, a, s) : (wpx == 1 ? launch<2, 1, G>(p, a, s) : launch<2, 2, G>(p, a, s));
 }
 
 // wave-specialised kernel (conv_bf16x3_ws_kernel): 64 oc x 16 rows x 32 px tiles, one 12-wave workgroup per CU
 template <int KS, int WOC, int CB>
-int launch_ws(Bf16Args a, hipStream_t s) {
-    a.c.tiles_y = gc::ceil_div(a.c.out_h, 16 / CB);
-    a.c.tiles_x = gc::ceil_div(a.c.out_w, 32 * CB);
-    const int tiles = a.c.tiles_x * a.c.tiles_y, ocb = a.c.N / (32 * WOC);
-    const long long wgs = (long long)tiles * a.c.B * ocb;
-    // One workgroup per CU is resident, so nothing overlaps a workgroup's start-up (two exposed load latencies) and its store drain:
-    // give every workgroup ALL the consecutive tiles its CU would get over the rounds of the launch (the staging waves then run ahead
-    // into the next tile while the multiplying waves store the current one).
-    a.tpb = (int)std::min<long long>(std::max<long long>((wgs + GC_WS_SLOTS - 1) / GC_WS_SLOTS, 1), tiles);
-    a.groups = gc::ceil_div(tiles, a.tpb);
-    const long long gx = (long long)a.groups * a.c.B;
-    if (gx > 2147483647LL) return gc::fail(GC_ERR_UNSUPPORTED, "gc_conv2d_bf16x3_f32: grid too large");
-    if (gc::probing()) return gc::probe_name("conv_bf16x3_ws_kernel<%d,%d,%d>|up1,down1,k%d", KS, WOC, CB, KS);
-    const bool plain = GC_WS_BARE && !a.c.bias && !a.c.noise && !a.c.act;
-    const int epk = !plain ? 0 : ((a.c.so || a.c.residual) ? 1 : 2);
-    const bool res = a.c.residual != nullptr;
-    if (epk == 2)             hipLaunchKernelGGL((conv_bf16x3_ws_kernel<KS, WOC, CB, 2, false>), dim3((unsigned)gx, ocb), dim3(768), 0, s, a);
-    else if (epk == 1 && res) hipLaunchKernelGGL((conv_bf16x3_ws_kernel<KS, WOC, CB, 1, true>), dim3((unsigned)gx, ocb), dim3(768), 0, s, a);
-    else if (epk == 1)        hipLaunchKernelGGL((conv_bf16x3_ws_kernel<KS, WOC, CB, 1, false>), dim3((unsigned)gx, ocb), dim3(768), 0, s, a);
-    else if (res)             hipLaunchKernelGGL((conv_bf16x3_ws_kernel<KS, WOC, CB, 0, true>), dim3((unsigned)gx, ocb), dim3(768), 0, s, a);
-    else                      hipLaunchKernelGGL((conv_bf16x3_ws_kernel<KS, WOC, CB, 0, false>), dim3((unsigned)gx, ocb), dim3(768), 0, s, a);
+int launch_ws_inst(const ConvPlan& p, const Bf16Args& a, hipStream_t s) {
+    const dim3 grid((unsigned)p.gx, a.c.N / (32 * WOC));
+    with_ws_epilogue(a.c, GC_WS_BARE, [&](auto epk, auto res) {
+        hipLaunchKernelGGL((conv_bf16x3_ws_kernel<KS, WOC, CB, decltype(epk)::value, decltype(res)::value>), grid, dim3(768), 0, s, a);
+    });
     return gc::check_launch("gc_conv2d_bf16x3_f32(ws)");
 }
 
-// the layers the wave-specialised kernel takes: whole 16-channel chunks and 64-channel output blocks, enough chunks per tile to
-// amortise its two-stage start-up, and enough tiles to give every CU a workgroup
-inline bool ws_eligible(const Bf16Args& a) {
+template <int KS>
+int launch_ws(const ConvPlan& p, const Bf16Args& a, hipStream_t s) {
+    const int woc = p.t[0], cb = p.t[1];
+    if (woc == 2) return cb == 2 ? launch_ws_inst<KS, 2, 2>(p, a, s) : launch_ws_inst<KS, 2, 1>(p, a, s);      // (4 x 128 px tiles of 64 channels do not fit two LDS stages)
+    return cb == GC_WS_WIDE_CB32 ? launch_ws_inst<KS, 1, GC_WS_WIDE_CB32>(p, a, s) : (cb == 2 ? launch_ws_inst<KS, 1, 2>(p, a, s) : launch_ws_inst<KS, 1, 1>(p, a, s));
+}
+
+// the kernels of one geometry, in the order plan_geom considers them
+template <class G>
+int launch_geom(const ConvPlan& p, const Bf16Args& a, hipStream_t s) {
+    if constexpr (G::UP == 1 && G::DOWN == 1) { if (p.path == ConvPath::WS) return launch_ws<G::KS>(p, a, s); }
+#ifndef GC_SINGLE
+    if constexpr (G::DOWN == 2 && G::KS == 3) { if (p.path == ConvPath::S2WS) return launch_s2ws(p, a, s); }
+#endif
+    return launch_one_role<G>(p, a, s);
+}
+
+// ---- the plan: every decision of a forward launch, taken here and nowhere else ----
+
+template <int WOC, int WPX, class G>
+void set_one_role(ConvPlan& p) {
+    using C = BCfg<1, 4, WOC, WPX, G::UP, G::DOWN, G::KS>;
+    p.path = ConvPath::ONE_ROLE;
+    p.t[0] = 1; p.t[1] = 4; p.t[2] = WOC; p.t[3] = WPX;
+    p.tile_h = C::TPH; p.tile_w = 32; p.oct = C::OCT;
+}
+
+template <int KS, int WOC, int CB>
+void set_ws(ConvPlan& p) {
+    using C = BCfg<1, 8, WOC, 2, 1, 1, KS, CB>;          // the configuration of conv_bf16x3_ws_kernel<KS, WOC, CB>
+    p.path = ConvPath::WS;
+    p.t[0] = WOC; p.t[1] = CB; p.t[2] = p.t[3] = 0;
+    p.tile_h = C::TPH; p.tile_w = 32 * CB; p.oct = C::OCT;
+}
+
+// the layers the wave-specialised kernel takes (p: their unsplit one-role plan, replaced when it does): whole 16-channel chunks and 32- / 64-channel
+// output blocks, enough chunks per tile to amortise its two-stage start-up, and enough tiles to give every CU a workgroup
+template <int KS>
+bool plan_ws(const gc_conv_desc* d, ConvPlan& p) {
 #ifdef GC_NO_WS
     return false;
 #endif
-    const ConvArgs& c = a.c;
-    const int oct = c.N % 64 == 0 ? 64 : 32;          // 32-channel output blocks for the layers whose N is not a multiple of 64 (the 1024^2 layers: N = 32)
-    if (a.k_per_split || c.K % KCB != 0 || c.N % 32 != 0 || c.K < (oct == 64 ? GC_WS_MIN_K : GC_WS_MIN_K32) || c.out_w < 32 || c.out_h < 16) return false;
-    const long long wgs = (long long)gc::ceil_div(c.out_w, 32) * gc::ceil_div(c.out_h, 16) * c.B * (c.N / oct);
-    return wgs >= 192;
+    const bool oc64 = d->out_ch % 64 == 0;          // 32-channel output blocks for the layers whose N is not a multiple of 64 (the 1024^2 layers: N = 32)
+    if (d->in_ch % KCB != 0 || d->out_ch % 32 != 0 || d->in_ch < (oc64 ? GC_WS_MIN_K : GC_WS_MIN_K32) || d->out_w < 32 || d->out_h < 16) return false;
+    ConvPlan q = p;
+    if (oc64) set_ws<KS, 2, 1>(q); else set_ws<KS, 1, 1>(q);
+    plan_tiles(q, d->out_h, d->out_w);
+    if ((long long)q.tiles_x * q.tiles_y * d->batch * (d->out_ch / q.oct) < 192) return false;
+    // wide tiles (8 rows x 64 px) where HBM, not the matrix pipe, bounds the layer: few input channels per output byte
+    if (d->in_ch <= GC_WS_WIDE_MAX_K && d->out_w >= 64) {
+        if (oc64) set_ws<KS, 2, 2>(q);
+        else if (d->out_w >= 128) set_ws<KS, 1, GC_WS_WIDE_CB32>(q);
+        else set_ws<KS, 1, 2>(q);
+        plan_tiles(q, d->out_h, d->out_w);
+    }
+    plan_resident(q, d);
+    p = q;
+    return true;
 }
 
-template <int UP, int DOWN, int KS>
-int dispatch(const Bf16Args& a, hipStream_t s) {
-    if constexpr (UP == 1 && DOWN == 1) {
-        if (ws_eligible(a)) {
-            // wide tiles (8 rows x 64 px) where HBM, not the matrix pipe, bounds the layer: few input channels per output byte
-            const bool wide = a.c.K <= GC_WS_WIDE_MAX_K && a.c.out_w >= 64;
-            if (a.c.N % 64 == 0) return wide ? launch_ws<KS, 2, 2>(a, s) : launch_ws<KS, 2, 1>(a, s);      // (4 x 128 px tiles of 64 channels do not fit two LDS stages)
-            return wide ? (a.c.out_w >= 128 ? launch_ws<KS, 1, GC_WS_WIDE_CB32>(a, s) : launch_ws<KS, 1, 2>(a, s)) : launch_ws<KS, 1, 1>(a, s);
-        }
+template <class G>
+void plan_geom(const gc_conv_desc* d, size_t room, ConvPlan& p) {
+    constexpr int UP = G::UP, DOWN = G::DOWN, KS = G::KS;
+    const int qh = gc::ceil_div(d->out_h, UP), qw = gc::ceil_div(d->out_w, UP);
+    if (DOWN == 2) {
+        // patch extents double: 4-row tiles only
+        if (d->out_ch <= 32) set_one_role<1, 1, G>(p); else set_one_role<2, 1, G>(p);
+    } else if (d->out_ch <= 32) {
+        set_one_role<1, 2, G>(p);                  // 32oc x (8 rows x 32 px)
+    } else {
+        // 64oc x (8 rows x 32 px) unless that leaves most CUs idle (32x32 / 64x64 planes at batch 4): 4-row tiles
+        set_one_role<2, 2, G>(p);
+        plan_tiles(p, qh, qw);
+        if ((long long)p.tiles_x * p.tiles_y * UP * UP * d->batch * gc::ceil_div(d->out_ch, p.oct) < 512) set_one_role<2, 1, G>(p);
     }
-    if constexpr (DOWN == 2) {
+    plan_tiles(p, qh, qw);
+    // small planes split over K, from the tiles of the instance chosen above (round 5: a plan of its own assumed eight rows throughout and cut the stride-1
+    // layers into twice the slices they needed -- 512 -> 512 @32^2: B = 4 79 -> 71 us with two slices instead of four, B = 8 133 -> 114 us unsplit; the partial
+    // sums are the cost of a slice).  A split launch stays here: the wave-specialised kernels below take unsplit launches only.
+    if (UP == 1) plan_split(p, d, room);
+    if (!p.split) {
+        if constexpr (UP == 1 && DOWN == 1) { if (plan_ws<KS>(d, p)) return; }
 #ifndef GC_SINGLE
         // round 6: the large 3x3 layers on the wave-specialised stride-2 kernel (conv_s2ws.hip: E / O half stages, 128 oc x 8 rows x 32 px tiles)
-        if constexpr (KS == 3) { if (s2ws_eligible(a)) return launch_s2ws(a, s); }
+        if constexpr (DOWN == 2 && KS == 3) { if (plan_s2ws(d, p)) return; }
 #endif
-        // patch extents double: 4-row tiles only
-        if (a.c.N <= 32) return launch<1, 4, 1, 1, UP, DOWN, KS>(a, s);
-        return launch<1, 4, 2, 1, UP, DOWN, KS>(a, s);
-    } else {
-        if (a.c.N <= 32) return launch<1, 4, 1, 2, UP, DOWN, KS>(a, s);     // 32oc x (8 rows x 32 px)
-        // 64oc x (8 rows x 32 px) unless that leaves most CUs idle (32x32 / 64x64 planes at batch 4): 4-row tiles
-        const int qw = gc::ceil_div(a.c.out_w, UP), qh = gc::ceil_div(a.c.out_h, UP);
-        const long long big = (long long)gc::ceil_div(qw, 32) * gc::ceil_div(qh, 8) * UP * UP * a.c.B * gc::ceil_div(a.c.N, 64);
-        if (big < 512) return launch<1, 4, 2, 1, UP, DOWN, KS>(a, s);
-        return launch<1, 4, 2, 2, UP, DOWN, KS>(a, s);
     }
+    // tiles per workgroup: as many as keep >= 8 workgroups per CU-slot pair (2048 on 256 CUs x 2) in the launch, at most 8;
+    // few channel chunks per tile is where the per-tile latencies dominate, many chunks need no help
+    const int tiles = p.tiles_x * p.tiles_y;
+    if (UP == 1 && !p.split) {
+        const long long wgs = (long long)tiles * d->batch * gc::ceil_div(d->out_ch, p.oct);
+        const int nchunks = gc::ceil_div(d->in_ch, KCB);
+        int want = nchunks <= 2 ? 8 : (nchunks <= 4 ? 4 : (nchunks <= 8 ? 2 : 1));
+        while (want > 1 && wgs / want < 2048) want >>= 1;
+        p.tpb = want;
+    }
+    p.groups = gc::ceil_div(tiles, p.tpb);
+    p.gx = (long long)p.groups * UP * UP * d->batch;
 }
 
-// shapes the split-bf16 kernel is built for; everything else runs on the exact fp32 kernel
+// shapes the split-bf16 kernels are built for; everything else runs on the exact fp32 kernels
 bool eligible(const gc_conv_desc* d) {
     const int qw = gc::ceil_div(d->out_w, d->up);
     // 9 .. 16-pixel rows fill part of the 32-pixel tile only, yet beat the fp32 MFMA path (512 -> 512 @16^2, B = 8: 97 vs 201 us;
@@ -895,46 +929,33 @@ bool eligible(const gc_conv_desc* d) {
     return d->pad_x >= 1 && d->pad_x <= 2;      // up = 2: phase rows start 0 or 1 floats before the boundary only for these
 }
 
-// Planes of 9 .. 32 pixels (the 16^2 / 32^2 layers, 512 channels) give the launch only B * tiles * N / 64 = 64 .. 256 workgroups, each
-// walking all 32 channel chunks one after the other with nothing to hide the load latency behind (512 -> 512 @16^2, B = 4: 88 us for
-// 4.8 GFLOP).  Splitting K over blockIdx.z fills the chip and shortens the dependent chain; slices of >= 4 chunks.
-#ifndef GC_CT_SPLITK
-#define GC_CT_SPLITK 1        // transposed 3x3 convolutions on small planes split over the input channels
-#endif
-#ifndef GC_SPLIT_TARGET
-#define GC_SPLIT_TARGET 512   // workgroups a split launch aims for
-#endif
-struct SplitPlan { int slices, k_per_split; };
-SplitPlan plan_splitk_bf16(const gc_conv_desc* d) {
-    SplitPlan sp{1, 0};
-    if (d->in_ch < 128) return sp;
-    long long wgs;
-    if (d->up == 2) {
-        // the fused transposed kernel (round 5: 512 -> 512 @8^2 / @16^2 were 64 / 160 workgroups walking all 32 chunks: 90 us each whatever the plane);
-        // dense rows only (the finish pass writes dense rows), > 32 output channels (dispatch_t's 64-channel tiles)
-        if (!GC_CT_SPLITK || d->kh != 3 || d->pad_y != 2 || d->pad_x != 2 || d->out_ch <= 32 || (d->out_pitch != 0 && d->out_pitch != d->out_w)) return sp;
-        const int qw = gc::ceil_div(d->out_w, 2), qh = gc::ceil_div(d->out_h, 2);
-        const bool narrow = gc::ceil_div(qw, 16) * 16 < gc::ceil_div(qw, 32) * 32;
-        wgs = (long long)gc::ceil_div(qw, narrow ? 16 : 32) * gc::ceil_div(qh, narrow ? 8 : 4) * d->batch * gc::ceil_div(d->out_ch, 64);
-    } else {
-        // tile rows as dispatch() picks them: 4 at stride 2; at stride 1 eight unless that gives < 512 workgroups, then four (round 5: this plan
-        // assumed eight rows throughout and cut the stride-1 layers into twice the slices they needed -- 512 -> 512 @32^2: B = 4 79 -> 71 us with
-        // two slices instead of four, B = 8 133 -> 114 us unsplit; the partial sums are the cost of a slice)
-        int rows = d->down == 2 ? 4 : 8;
-        wgs = (long long)gc::ceil_div(d->out_w, 32) * gc::ceil_div(d->out_h, rows) * d->batch * gc::ceil_div(d->out_ch, 64);
-        if (d->down == 1 && d->out_ch > 32 && wgs < 512) wgs = (long long)gc::ceil_div(d->out_w, 32) * gc::ceil_div(d->out_h, 4) * d->batch * gc::ceil_div(d->out_ch, 64);
-    }
-    const int want = (int)std::min<long long>(GC_SPLIT_TARGET / std::max<long long>(wgs, 1), d->in_ch / 64);
-    if (want <= 1) return sp;
-    sp.k_per_split = gc::ceil_div(gc::ceil_div(d->in_ch, want), KCB) * KCB;
-    sp.slices = gc::ceil_div(d->in_ch, sp.k_per_split);
-    if (sp.slices <= 1) { sp.slices = 1; sp.k_per_split = 0; }
-    return sp;
+// THE decision of a forward launch in split-bf16 / plain-bf16 arithmetic.  ep: the launch's epilogue (null for the queries; only the GC_CTWS
+// experiments look at it); room: the bytes the caller brought for the K slices (0 for the queries and the probe: they see the unsplit decision).
+ConvPlan plan_conv(const gc_conv_desc* d, const gc_conv_epilogue* ep, size_t room) {
+    ConvPlan p;
+    if (!eligible(d)) return p;
+    if (d->kh == 3 && d->up == 2 && d->pad_y == 2 && d->pad_x == 2) plan_t(d, ep, room, p);       // the fused transposed kernel
+    else with_geom(d, [&](auto g) { plan_geom<decltype(g)>(d, room, p); });
+    return p;
 }
 
-size_t splitk_bytes(const gc_conv_desc* d) {
-    const SplitPlan sp = plan_splitk_bf16(d);
-    return sp.slices > 1 ? (size_t)sp.slices * d->batch * d->out_ch * d->out_h * d->out_w * sizeof(float) : 0;
+// ... and what follows from it for a caller's buffers
+bool reads_pitched_input(const gc_conv_desc* d, const ConvPlan& p) { return p.path != ConvPath::F32 && d->up == 1 && d->down == 2; }      // conv_bf16x3_kernel and conv_s2ws_bf16x3_kernel at stride 2
+size_t packed_weight_bytes(const gc_conv_desc* d, const ConvPlan& p) { return p.path != ConvPath::F32 ? 2 * packed_units(d) * sizeof(uint4) : 0; }      // hi and lo halves
+
+int probe_conv(const gc_conv_desc* d, const ConvPlan& p) {
+    const int* t = p.t;
+    switch (p.path) {
+    case ConvPath::ONE_ROLE:  return gc::probe_name("conv_bf16x3_kernel<%d,%d,%d,%d>|up%d,down%d,k%d", t[0], t[1], t[2], t[3], d->up, d->down, d->kh);
+    case ConvPath::WS:        return gc::probe_name("conv_bf16x3_ws_kernel<%d,%d,%d>|up1,down1,k%d", d->kh, t[0], t[1], d->kh);
+    case ConvPath::S2WS:      return gc::probe_name("conv_s2ws_bf16x3_kernel<%d>|up1,down2,k3", t[0]);
+    case ConvPath::CT:        return gc::probe_name("convt_fused_bf16x3_kernel<%d,%d,%d,%d>|up2,down1,k3", t[0], t[1], t[2], t[3]);
+    case ConvPath::CT_EDGE:   return gc::probe_name("convt_fused_bf16x3_kernel<%d,%d,%d,%d>+edge|up2,down1,k3", t[0], t[1], t[2], t[3]);
+    case ConvPath::CTWS:      return gc::probe_name("convt_bf16x3_ws_kernel<%d,%d>|up2,down1,k3", t[0], t[1]);
+    case ConvPath::CTWS_EDGE: return gc::probe_name("convt_bf16x3_ws_kernel<%d,%d>+edge|up2,down1,k3", t[0], t[1]);
+    case ConvPath::F32:       break;      // named by the fp32 family itself
+    }
+    return gc::fail(GC_ERR_BAD_ARG, "gc_conv2d_bf16x3_f32: no kernel to name");
 }
 
 }  // namespace
@@ -945,33 +966,31 @@ size_t splitk_bytes(const gc_conv_desc* d) {
 #else
 extern "C" size_t gc_conv2d_bf16x3_workspace(const gc_conv_desc* d) {
     if (!d || d->in_ch <= 0 || d->out_ch <= 0 || d->kh <= 0 || d->kw <= 0) return 0;
-    if (!eligible(d)) return conv2d_f32_workspace(d);        // runs on the fp32 kernel: split-K partial sums (small planes) or nothing
-    const size_t units = (size_t)d->kh * d->kw * ((d->in_ch + 7) / 8) * d->out_ch;
-    return 2 * units * sizeof(uint4) + splitk_bytes(d);      // the split weights (gc_conv2d_fused_bf16x3_f32 packs them here), then the K slices
+    const ConvPlan p = plan_conv(d, nullptr, 0);
+    if (p.path == ConvPath::F32) return conv2d_f32_workspace(d);        // runs on the fp32 kernel: split-K partial sums (small planes) or nothing
+    return packed_weight_bytes(d, p) + p.slice_bytes(d);      // the split weights (gc_conv2d_fused_bf16x3_f32 packs them here), then the K slices
 }
 
 extern "C" size_t gc_conv2d_bf16x3_splitk_bytes(const gc_conv_desc* d) {
-    if (!d || d->batch <= 0 || d->in_ch <= 0 || d->out_ch <= 0 || d->kh <= 0 || d->kw <= 0 || !eligible(d)) return 0;
-    return splitk_bytes(d);
+    if (!d || d->batch <= 0 || d->in_ch <= 0 || d->out_ch <= 0 || d->kh <= 0 || d->kw <= 0) return 0;
+    return plan_conv(d, nullptr, 0).slice_bytes(d);
 }
-#endif
 
-#ifndef GC_SINGLE
 extern "C" int gc_conv2d_out_pitch(const gc_conv_desc* d, int mode) {
     if (!d || mode == 0 || d->in_ch <= 0 || d->out_ch <= 0 || d->out_w <= 0) return 0;          // the fp32 kernels write dense rows
-    if (!(eligible(d) && d->kh == 3 && d->kw == 3 && d->up == 2 && d->pad_y == 2 && d->pad_x == 2)) return 0;
+    if (!plan_conv(d, nullptr, 0).fused_transposed()) return 0;
     if (d->out_w % 32 == 0 || d->out_w < 129) return 0;       // already aligned, or too small to matter
     return (d->out_w + 31) / 32 * 32;
 }
 
 extern "C" int gc_conv2d_in_pitch_ok(const gc_conv_desc* d, int mode, int wgrad) {
     if (!d || mode == 0 || d->in_ch <= 0 || d->out_ch <= 0 || d->up != 1 || d->down != 2) return 0;
-    return wgrad ? (wg_eligible(d) ? 1 : 0) : (eligible(d) ? 1 : 0);
+    return wgrad ? (wg_eligible(d) ? 1 : 0) : (reads_pitched_input(d, plan_conv(d, nullptr, 0)) ? 1 : 0);
 }
 
 extern "C" size_t gc_conv2d_bf16x3_packed_bytes(const gc_conv_desc* d) {
-    if (!d || d->in_ch <= 0 || d->out_ch <= 0 || d->kh <= 0 || d->kw <= 0 || !eligible(d)) return 0;
-    return 2 * (size_t)d->kh * d->kw * ((d->in_ch + 7) / 8) * d->out_ch * sizeof(uint4);
+    if (!d || d->in_ch <= 0 || d->out_ch <= 0 || d->kh <= 0 || d->kw <= 0) return 0;
+    return packed_weight_bytes(d, plan_conv(d, nullptr, 0));
 }
 
 extern "C" int gc_conv2d_pack_weights_bf16x3(const gc_conv_desc* d, const float* w, void* packed, size_t packed_bytes, gc_stream_t stream) {
@@ -982,7 +1001,7 @@ extern "C" int gc_conv2d_pack_weights_bf16x3(const gc_conv_desc* d, const float*
     if (!w || !packed || packed_bytes < need || (reinterpret_cast<uintptr_t>(packed) & 15))
         return gc::fail(GC_ERR_WORKSPACE, "gc_conv2d_pack_weights_bf16x3: buffer %zu < %zu bytes (or null / not 16-byte aligned)", packed_bytes, need);
     const int kgroups = (d->in_ch + 7) / 8, taps = d->kh * d->kw;
-    const size_t units = (size_t)taps * kgroups * d->out_ch;
+    const size_t units = packed_units(d);
     uint4* wh = static_cast<uint4*>(packed);
     hipLaunchKernelGGL(pack_weights_kernel, dim3((unsigned)std::min<size_t>((units + 255) / 256, 4096)), dim3(256), 0, (hipStream_t)stream,
                        w, wh, wh + units, taps, d->in_ch, d->out_ch, kgroups);
@@ -1004,7 +1023,7 @@ extern "C" int gc_conv2d_pack_weights_bf16x3_grouped(const gc_wpack_group* group
             if (!g.w || !g.packed || g.packed_bytes < need || (reinterpret_cast<uintptr_t>(g.packed) & 15))
                 return gc::fail(GC_ERR_WORKSPACE, "gc_conv2d_pack_weights_bf16x3_grouped: group %d: buffer %zu < %zu bytes (or null / not 16-byte aligned)", first + i, (size_t)g.packed_bytes, need);
             const int kgroups = (g.desc.in_ch + 7) / 8, taps = g.desc.kh * g.desc.kw;
-            const size_t units = (size_t)taps * kgroups * g.desc.out_ch;
+            const size_t units = packed_units(&g.desc);
             uint4* wh = static_cast<uint4*>(g.packed);
             a.g[i] = PackGroup{g.w, wh, wh + units, taps, g.desc.in_ch, g.desc.out_ch, kgroups, (int)blocks};
             blocks += (long long)((units + 255) / 256);
@@ -1024,46 +1043,39 @@ extern "C" int gc_conv2d_fused_bf16x3_packed_f32(const gc_conv_desc* d, const fl
     if (!x || !w || !y) return gc::fail(GC_ERR_BAD_ARG, "gc_conv2d_bf16x3_f32: null pointer");
     if (d->batch == 0) return GC_OK;
     if ((rc = validate_epilogue(ep, "gc_conv2d_bf16x3_f32"))) return rc;
-    if (d->in_pitch != 0 && d->in_pitch != d->in_w && !(eligible(d) && d->up == 1 && d->down == 2))
+    // small planes: split over K when the caller brought room for the slices (gc_conv2d_bf16x3_splitk_bytes)
+    const ConvPlan p = plan_conv(d, ep, workspace && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0 ? workspace_bytes : 0);
+    if (d->in_pitch != 0 && d->in_pitch != d->in_w && !reads_pitched_input(d, p))
         return gc::fail(GC_ERR_UNSUPPORTED, "gc_conv2d_bf16x3_f32: in_pitch %d: only the split-bf16 stride-2 kernel reads pitched rows (gc_conv2d_in_pitch_ok)", d->in_pitch);
-    const bool pitched_ok = eligible(d) && d->kh == 3 && d->up == 2 && d->pad_y == 2 && d->pad_x == 2;      // the fused transposed kernel
-    if (!dense_output(d) && !pitched_ok)
+    if (!dense_output(d) && !p.fused_transposed())
         return gc::fail(GC_ERR_UNSUPPORTED, "gc_conv2d_bf16x3_f32: out_pitch %d: only the fused transposed 3x3 convolution writes pitched rows (gc_conv2d_out_pitch)", d->out_pitch);
-    if (!eligible(d)) return conv2d_f32_ws(d, x, w, in_scale, out_scale, ep, y, workspace, workspace_bytes, stream);
-    const size_t need = gc_conv2d_bf16x3_packed_bytes(d);
+    if (p.path == ConvPath::F32) return conv2d_f32_ws(d, x, w, in_scale, out_scale, ep, y, workspace, workspace_bytes, stream);
+    const size_t need = packed_weight_bytes(d, p);
     if (!packed || packed_bytes < need || (reinterpret_cast<uintptr_t>(packed) & 15))
         return gc::fail(GC_ERR_WORKSPACE, "gc_conv2d_bf16x3_f32: packed weights %zu < %zu bytes (or null / not 16-byte aligned)", packed_bytes, need);
+    // (the probe names the main region + edge forms before their grid is looked at)
+    if (p.gx > 2147483647LL && !(gc::probing() && p.edge())) return gc::fail(GC_ERR_UNSUPPORTED, "gc_conv2d_bf16x3_f32: grid too large");
+    if (gc::probing()) return probe_conv(d, p);
     hipStream_t s = (hipStream_t)stream;
-    const int kgroups = (d->in_ch + 7) / 8, taps = d->kh * d->kw;
-    const size_t units = (size_t)taps * kgroups * d->out_ch;
     const uint4* wh = static_cast<const uint4*>(packed);
-    const uint4* wl = wh + units;
     Bf16Args a{{x, w, in_scale, out_scale, y, d->batch, d->in_ch, d->out_ch, d->in_h, d->in_w, d->out_h, d->out_w,
-                d->pad_y, d->pad_x, 0, 0}, wh, wl, kgroups, 1, 1, 0, nullptr, 0, d->out_pitch ? d->out_pitch : d->out_w, d->in_pitch ? d->in_pitch : d->in_w};
+                d->pad_y, d->pad_x, 0, 0}, wh, wh + packed_units(d), (d->in_ch + 7) / 8, p.tpb, p.groups, 0, nullptr, 0, d->out_pitch ? d->out_pitch : d->out_w, d->in_pitch ? d->in_pitch : d->in_w};
     set_epilogue(a.c, ep);
-    // small planes: split over K when the caller brought room for the slices (gc_conv2d_bf16x3_splitk_bytes)
-    const SplitPlan sp = plan_splitk_bf16(d);
-    const size_t slice_bytes = splitk_bytes(d);
-    const bool split = sp.slices > 1 && workspace && workspace_bytes >= slice_bytes && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0;
     ConvArgs fin = a.c;
-    if (split) {
+    a.c.tiles_x = p.tiles_x;
+    a.c.tiles_y = p.tiles_y;
+    if (p.split) {
+        // the slices are raw partial sums; the finish pass applies out_scale and the epilogue
         a.c.so = nullptr;
         set_epilogue(a.c, nullptr);
-        a.k_per_split = sp.k_per_split;
+        a.k_per_split = p.k_per_split;
         a.part = static_cast<float*>(workspace);
         a.per_slice = (long long)d->batch * d->out_ch * d->out_h * d->out_w;
     }
-    if (d->kh == 3) {
-        if (d->up == 2 && d->pad_y == 2 && d->pad_x == 2) rc = dispatch_t(a, s);
-        else if (d->up == 2) return dispatch<2, 1, 3>(a, s);
-        else rc = d->down == 2 ? dispatch<1, 2, 3>(a, s) : dispatch<1, 1, 3>(a, s);
-    } else {
-        if (d->up == 2) return dispatch<2, 1, 1>(a, s);
-        rc = d->down == 2 ? dispatch<1, 2, 1>(a, s) : dispatch<1, 1, 1>(a, s);
-    }
-    if (rc || !split) return rc;
+    rc = p.fused_transposed() ? launch_t(p, a, s) : with_geom(d, [&](auto g) { return launch_geom<decltype(g)>(p, a, s); });
+    if (rc || !p.split) return rc;
     fin.part = a.part;
-    return launch_splitk_finish(fin, sp.slices, a.per_slice, s);
+    return launch_splitk_finish(fin, p.slices, a.per_slice, s);
 }
 
 #ifndef GC_SINGLE

@@ -64,6 +64,16 @@
 #ifndef GC_WS_BARE
 #define GC_WS_BARE 1         // reduced epilogues (EPK 1 / 2) of the wave-specialised kernel for launches without bias / noise / activation (0: always the full epilogue)
 #endif
+// Planes of 9 .. 32 pixels (the 16^2 / 32^2 layers, 512 channels) give the launch only B * tiles * N / 64 = 64 .. 256 workgroups, each
+// walking all 32 channel chunks one after the other with nothing to hide the load latency behind (512 -> 512 @16^2, B = 4: 88 us for
+// 4.8 GFLOP).  Splitting K over blockIdx.z fills the chip and shortens the dependent chain; slices of >= 4 chunks.
+#ifndef GC_CT_SPLITK
+#define GC_CT_SPLITK 1        // transposed 3x3 convolutions on small planes split over the input channels
+#endif
+#ifndef GC_SPLIT_TARGET
+#define GC_SPLIT_TARGET 512   // workgroups a split launch aims for
+#endif
+#include <algorithm>
 
 
 namespace gcconv {
@@ -86,9 +96,78 @@ struct Bf16Args {
     int in_pitch;                       // floats between input rows (conv_bf16x3_kernel; in_w when dense)
 };
 
-// defined in conv_s2ws.hip (split build only): the wave-specialised stride-2 3x3 kernel and the shapes it takes
-bool s2ws_eligible(const Bf16Args& a);
-int launch_s2ws(Bf16Args a, hipStream_t s);
+// The decision of ONE forward launch, taken once by plan_conv (conv_bf16x3.hip) and read by everything else: the argument checks, the size and pitch
+// queries, the probe name and the launchers (which only instantiate what it says).
+enum class ConvPath {
+    F32,            // not a shape of these kernels: the exact fp32 family (conv.hip)
+    ONE_ROLE,       // conv_bf16x3_kernel<t0, t1, t2, t3, up, down, k>
+    WS,             // conv_bf16x3_ws_kernel<k, t0, t1>
+    S2WS,           // conv_s2ws_bf16x3_kernel<t0>
+    CT, CT_EDGE,    // convt_fused_bf16x3_kernel<t0, t1, t2, t3>; _EDGE: over the H x W main region, convt_edge_bf16x3_kernel does the rest
+    CTWS, CTWS_EDGE // convt_bf16x3_ws_kernel<t0, t1> (the GC_CTWS experiments)
+};
+struct ConvPlan {
+    ConvPath path = ConvPath::F32;
+    int t[4] = {0, 0, 0, 0};            // the template arguments of the instance (see ConvPath)
+    int tile_h = 1, tile_w = 1, oct = 1;      // a workgroup's tile, from the instance's own config constants: rows x columns (of the phase sub-grid when up = 2) x output channels
+    int slices = 1, k_per_split = 0;    // the split over the input channels as the queries size it ...
+    bool split = false;                 // ... and whether THIS launch runs split: the caller brought room for the slices.  A split launch stays on the one-role kernels.
+    int tiles_x = 1, tiles_y = 1, tpb = 1, groups = 1;      // pixel tiles, tiles per workgroup, workgroups per (sample, phase)
+    long long gx = 0;                   // grid x
+    bool fused_transposed() const { return path >= ConvPath::CT; }      // the one family that writes pitched output rows
+    bool edge() const { return path == ConvPath::CT_EDGE || path == ConvPath::CTWS_EDGE; }
+    size_t slice_bytes(const gc_conv_desc* d) const { return slices > 1 ? (size_t)slices * d->batch * d->out_ch * d->out_h * d->out_w * sizeof(float) : 0; }
+};
+
+// units of 8 bf16 in ONE half (hi or lo) of the packed weights: [tap][ceil(K / 8)][N]
+inline size_t packed_units(const gc_conv_desc* d) { return (size_t)d->kh * d->kw * ((d->in_ch + 7) / 8) * d->out_ch; }
+
+// tiles of the plan's tile over a qh x qw plane, and from them the split over K of a one-role instance: as many slices as bring the launch to
+// GC_SPLIT_TARGET workgroups, of >= 64 channels each.  room: the bytes the caller brought for the slices.
+inline void plan_tiles(ConvPlan& p, int qh, int qw) {
+    p.tiles_y = gc::ceil_div(qh, p.tile_h);
+    p.tiles_x = gc::ceil_div(qw, p.tile_w);
+}
+inline void plan_split(ConvPlan& p, const gc_conv_desc* d, size_t room) {
+    if (d->in_ch < 128) return;
+    const long long wgs = (long long)p.tiles_x * p.tiles_y * d->batch * gc::ceil_div(d->out_ch, p.oct);
+    const int want = (int)std::min<long long>(GC_SPLIT_TARGET / std::max<long long>(wgs, 1), d->in_ch / 64);
+    if (want <= 1) return;
+    const int kps = gc::ceil_div(gc::ceil_div(d->in_ch, want), KCB) * KCB, slices = gc::ceil_div(d->in_ch, kps);
+    if (slices <= 1) return;
+    p.slices = slices;
+    p.k_per_split = kps;
+    p.split = room >= p.slice_bytes(d);
+}
+// The wave-specialised kernels keep ONE workgroup resident per CU, so nothing overlaps a workgroup's start-up (two exposed load latencies) and its
+// store drain: every workgroup takes ALL the consecutive tiles its CU would get over the rounds of the launch (the staging waves then run ahead
+// into the next tile while the multiplying waves store the current one).
+inline void plan_resident(ConvPlan& p, const gc_conv_desc* d) {
+    const int tiles = p.tiles_x * p.tiles_y;
+    const long long wgs = (long long)tiles * d->batch * (d->out_ch / p.oct);
+    p.tpb = (int)std::min<long long>(std::max<long long>((wgs + GC_WS_SLOTS - 1) / GC_WS_SLOTS, 1), tiles);
+    p.groups = gc::ceil_div(tiles, p.tpb);
+    p.gx = (long long)p.groups * d->batch;
+}
+
+// The reduced epilogues of the wave-specialised kernels -- EPK 0: the full fused epilogue, 1: out_scale and / or residual only, 2: nothing; RES: a
+// residual is added -- as the template arguments of the one instance a launch needs: launch(EPK constant, RES constant).
+template <class Launch>
+void with_ws_epilogue(const ConvArgs& c, bool bare, Launch&& launch) {
+    const bool plain = bare && !c.bias && !c.noise && !c.act, res = c.residual != nullptr;
+    const int epk = !plain ? 0 : ((c.so || res) ? 1 : 2);
+    using std::integral_constant;
+    if (epk == 2)             launch(integral_constant<int, 2>{}, std::false_type{});
+    else if (epk == 1 && res) launch(integral_constant<int, 1>{}, std::true_type{});
+    else if (epk == 1)        launch(integral_constant<int, 1>{}, std::false_type{});
+    else if (res)             launch(integral_constant<int, 0>{}, std::true_type{});
+    else                      launch(integral_constant<int, 0>{}, std::false_type{});
+}
+
+// defined in conv_s2ws.hip (split build only): the wave-specialised stride-2 3x3 kernel; plan_s2ws turns an unsplit one-role plan into its own
+// (tiling and grid included) for the shapes the kernel takes and says whether it did
+bool plan_s2ws(const gc_conv_desc* d, ConvPlan& p);
+int launch_s2ws(const ConvPlan& p, const Bf16Args& a, hipStream_t s);
 
 // Host functions that cross the units built in BOTH arithmetics: an inline namespace per arithmetic keeps the split and the -DGC_SINGLE
 // definitions apart at link time (callers write the plain name).
@@ -98,7 +177,9 @@ int launch_s2ws(Bf16Args a, hipStream_t s);
 #define GC_ARITH split
 #endif
 inline namespace GC_ARITH {
-int dispatch_t(const Bf16Args& a, hipStream_t s);       // convt_bf16x3.hip: the transposed 3x3 stride-2 convolution (up = 2, pad' = 2)
+// convt_bf16x3.hip: the transposed 3x3 stride-2 convolution (up = 2, pad' = 2) -- its whole plan (ep: the launch's epilogue, read by the GC_CTWS experiments only) and its launcher
+void plan_t(const gc_conv_desc* d, const gc_conv_epilogue* ep, size_t room, ConvPlan& p);
+int launch_t(const ConvPlan& p, const Bf16Args& a, hipStream_t s);
 bool wg_eligible(const gc_conv_desc* d);                // wgrad_bf16x3.hip: shapes the split-bf16 weight-gradient kernels take
 }
 

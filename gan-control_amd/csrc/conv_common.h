@@ -118,6 +118,16 @@ inline int validate(const gc_conv_desc* d, const char* who, bool wgrad) {
 }
 
 
+// The compile-time geometries of the forward kernels: f(Geom<up, down, taps>) for the geometry of a validated descriptor (3x3 or 1x1 taps; up 2,
+// down 2 or neither)
+template <int UP_, int DOWN_, int KS_> struct Geom { static constexpr int UP = UP_, DOWN = DOWN_, KS = KS_; };
+template <class F>
+auto with_geom(const gc_conv_desc* d, F&& f) {
+    if (d->kh == 3) return d->up == 2 ? f(Geom<2, 1, 3>{}) : (d->down == 2 ? f(Geom<1, 2, 3>{}) : f(Geom<1, 1, 3>{}));
+    return d->up == 2 ? f(Geom<2, 1, 1>{}) : (d->down == 2 ? f(Geom<1, 2, 1>{}) : f(Geom<1, 1, 1>{}));
+}
+
+
 // Buffer-descriptor loads (cdna guide T8): address = descriptor base + scalar byte offset + 32-bit lane byte
 // offset -> no 64-bit VALU address arithmetic, and the hardware returns 0 for lane offsets >= the buffer size, so
 // out-of-image elements need no exec-mask branch: they are given the offset OOB (beyond any buffer used here).

@@ -337,28 +337,20 @@ __global__ __launch_bounds__(768) void conv_s2ws_bf16x3_kernel(Bf16Args a) {
 }
 
 template <int WOCB>
-int launch_s2ws_t(Bf16Args a, hipStream_t s) {
-    using C = S2Cfg<WOCB>;
-    a.c.tiles_y = gc::ceil_div(a.c.out_h, C::TR);
-    a.c.tiles_x = gc::ceil_div(a.c.out_w, 32);
-    const int tiles = a.c.tiles_x * a.c.tiles_y, ocb = a.c.N / C::OCT;
-    const long long wgs = (long long)tiles * a.c.B * ocb;
-    // one workgroup per CU is resident: a workgroup takes all the tiles its CU would get over the rounds of the launch
-    a.tpb = (int)std::min<long long>(std::max<long long>((wgs + GC_WS_SLOTS - 1) / GC_WS_SLOTS, 1), tiles);
-    a.groups = gc::ceil_div(tiles, a.tpb);
-    const long long gx = (long long)a.groups * a.c.B;
-    if (gx > 2147483647LL) return gc::fail(GC_ERR_UNSUPPORTED, "gc_conv2d_bf16x3_f32: grid too large");
-    if (gc::probing()) return gc::probe_name("conv_s2ws_bf16x3_kernel<%d>|up1,down2,k3", WOCB);
-    const bool plain = !a.c.bias && !a.c.noise && !a.c.act;
-    const int epk = !plain ? 0 : ((a.c.so || a.c.residual) ? 1 : 2);
-    const bool res = a.c.residual != nullptr;
-    const dim3 grid((unsigned)gx, ocb);
-    if (epk == 2)             hipLaunchKernelGGL((conv_s2ws_bf16x3_kernel<WOCB, 2, false>), grid, dim3(768), 0, s, a);
-    else if (epk == 1 && res) hipLaunchKernelGGL((conv_s2ws_bf16x3_kernel<WOCB, 1, true>), grid, dim3(768), 0, s, a);
-    else if (epk == 1)        hipLaunchKernelGGL((conv_s2ws_bf16x3_kernel<WOCB, 1, false>), grid, dim3(768), 0, s, a);
-    else if (res)             hipLaunchKernelGGL((conv_s2ws_bf16x3_kernel<WOCB, 0, true>), grid, dim3(768), 0, s, a);
-    else                      hipLaunchKernelGGL((conv_s2ws_bf16x3_kernel<WOCB, 0, false>), grid, dim3(768), 0, s, a);
+int launch_s2ws_t(const ConvPlan& p, const Bf16Args& a, hipStream_t s) {
+    const dim3 grid((unsigned)p.gx, a.c.N / S2Cfg<WOCB>::OCT);
+    with_ws_epilogue(a.c, true, [&](auto epk, auto res) {
+        hipLaunchKernelGGL((conv_s2ws_bf16x3_kernel<WOCB, decltype(epk)::value, decltype(res)::value>), grid, dim3(768), 0, s, a);
+    });
     return gc::check_launch("gc_conv2d_bf16x3_f32(stride 2, ws)");
+}
+
+template <int WOCB>
+void set_s2ws(ConvPlan& p) {
+    p.t[0] = WOCB;
+    p.tile_h = S2Cfg<WOCB>::TR;
+    p.tile_w = 32;
+    p.oct = S2Cfg<WOCB>::OCT;
 }
 
 }  // namespace
@@ -369,19 +361,26 @@ namespace gcconv {
 #define GC_S2WS 1             // 0: stride-2 3x3 convolutions stay on conv_bf16x3_kernel
 #endif
 
-// whole 16-channel chunks, whole 64-channel output blocks, no padding, enough tiles to give most CUs a workgroup
-bool s2ws_eligible(const Bf16Args& a) {
+// whole 16-channel chunks, whole 64-channel output blocks, no padding, every output pixel reading inside the plane (the kernel masks nothing:
+// anything else stays on the masked conv_bf16x3_kernel), enough tiles to give most CUs a workgroup
+bool plan_s2ws(const gc_conv_desc* d, ConvPlan& p) {
     if (!GC_S2WS) return false;
-    const ConvArgs& c = a.c;
-    if (a.k_per_split || c.K % KCB != 0 || c.K < 32 || c.K > MAX_K_BF16X3 || c.N % 64 != 0 || c.pad_x != 0 || c.pad_y != 0) return false;
-    if (c.out_w < 32 || c.out_h < 8) return false;
-    const int oct = c.N % 128 == 0 ? 128 : 64;          // (the 64-channel variant for N % 128 == 0 at few input channels: 64 -> 128 @513^2 measured 8 % slower on it)
-    const long long wgs = (long long)gc::ceil_div(c.out_w, 32) * gc::ceil_div(c.out_h, 8) * c.B * (c.N / oct);
-    return wgs >= GC_S2WS_MIN_WGS;
+    if (d->in_ch % KCB != 0 || d->in_ch < 32 || d->in_ch > MAX_K_BF16X3 || d->out_ch % 64 != 0 || d->pad_x != 0 || d->pad_y != 0) return false;
+    if (d->out_w < 32 || d->out_h < 8) return false;
+    if (d->in_h < 3 || d->in_w < 3 || d->out_h > (d->in_h - 3) / 2 + 1 || d->out_w > (d->in_w - 3) / 2 + 1) return false;
+    ConvPlan q = p;
+    // (the 64-channel variant for N % 128 == 0 at few input channels: 64 -> 128 @513^2 measured 8 % slower on it)
+    if (d->out_ch % 128 == 0) set_s2ws<2>(q); else set_s2ws<1>(q);
+    plan_tiles(q, d->out_h, d->out_w);
+    if ((long long)q.tiles_x * q.tiles_y * d->batch * (d->out_ch / q.oct) < GC_S2WS_MIN_WGS) return false;
+    q.path = ConvPath::S2WS;
+    plan_resident(q, d);
+    p = q;
+    return true;
 }
 
-int launch_s2ws(Bf16Args a, hipStream_t s) {
-    return a.c.N % 128 == 0 ? launch_s2ws_t<2>(a, s) : launch_s2ws_t<1>(a, s);
+int launch_s2ws(const ConvPlan& p, const Bf16Args& a, hipStream_t s) {
+    return p.t[0] == 2 ? launch_s2ws_t<2>(p, a, s) : launch_s2ws_t<1>(p, a, s);
 }
 
 }  // namespace gcconv

@@ -515,16 +515,14 @@ __global__ __launch_bounds__(256) void convt_edge_bf16x3_kernel(Bf16Args a) {
 
 // the launches that take the H x W main region + edge form: the (2H + 1) x (2W + 1) geometry, whole chunks and 64-channel output blocks, >= 256 input
 // channels (below that the layer is bound by its stores, not by its tiles), an H x W region that the 4 x 32 tile covers exactly, and >= 10 % fewer tiles
-inline bool ct_edge_eligible(const Bf16Args& a) {
-    const ConvArgs& c = a.c;
-    if (!GC_CT_EDGE || a.k_per_split || c.out_h != 2 * c.in_h + 1 || c.out_w != 2 * c.in_w + 1) return false;
-    if (c.K % KCB != 0 || c.K < 256 || c.K / KCB < 4 || c.N % 64 != 0 || c.in_w % 32 != 0 || c.in_h % 4 != 0) return false;
-    const int qh = c.in_h + 1, qw = c.in_w + 1;
-    const bool narrow = gc::ceil_div(qw, 16) * 16 < gc::ceil_div(qw, 32) * 32;
-    const long long full = (long long)gc::ceil_div(qw, narrow ? 16 : 32) * gc::ceil_div(qh, narrow ? 8 : 4), main_ = (long long)(c.in_w / 32) * (c.in_h / 4);
+// than the whole q-space has in the tiling `p` gave it
+inline bool ct_edge_eligible(const gc_conv_desc* d, const ConvPlan& p) {
+    if (!GC_CT_EDGE || d->out_h != 2 * d->in_h + 1 || d->out_w != 2 * d->in_w + 1) return false;
+    if (d->in_ch % KCB != 0 || d->in_ch < 256 || d->in_ch / KCB < 4 || d->out_ch % 64 != 0 || d->in_w % 32 != 0 || d->in_h % 4 != 0) return false;
+    const long long full = (long long)p.tiles_x * p.tiles_y, main_ = (long long)(d->in_w / 32) * (d->in_h / 4);
     // ... and enough workgroups for two per CU: with one per CU nothing overlaps its staging (512 -> 512 @32^2, B = 4: 256 workgroups, 127 -> 137 us;
     // 512 -> 256 @64^2, B = 2: 99 -> 133 us -- against B = 8 / B = 4 of the same layers: 226 -> 175, 197 -> 162 us; profiles/convt_ab_r05.log)
-    return 10 * main_ <= 9 * full && main_ * c.B * (c.N / 64) >= GC_CT_EDGE_MIN_WGS;
+    return 10 * main_ <= 9 * full && main_ * d->batch * (d->out_ch / 64) >= GC_CT_EDGE_MIN_WGS;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -561,15 +559,9 @@ inline bool ct_edge_eligible(const Bf16Args& a) {
 #endif      // GC_CTWS
 
 template <int WG_OC, int WG_PX, int WPX, int TPW>
-int launch_t(Bf16Args a, hipStream_t s, bool main_only = false) {
+int launch_t_inst(const ConvPlan& p, const Bf16Args& a, hipStream_t s) {
     using C = TCfg<WG_OC, WG_PX, WPX, TPW>;
-    const int qh = main_only ? a.c.in_h : gc::ceil_div(a.c.out_h, 2), qw = main_only ? a.c.in_w : gc::ceil_div(a.c.out_w, 2);     // main_only: the H x W region (convt_edge_bf16x3_kernel does the rest)
-    a.c.tiles_y = gc::ceil_div(qh, C::TQH);
-    a.c.tiles_x = gc::ceil_div(qw, TPW);
-    const long long gx = (long long)a.c.tiles_x * a.c.tiles_y * a.c.B;
-    if (gx > 2147483647LL) return gc::fail(GC_ERR_UNSUPPORTED, "gc_conv2d_bf16x3_f32: grid too large");
-    if (gc::probing()) return gc::probe_name("convt_fused_bf16x3_kernel<%d,%d,%d,%d>|up2,down1,k3", WG_OC, WG_PX, WPX, TPW);
-    dim3 grid((unsigned)gx, gc::ceil_div(a.c.N, C::OCT), a.k_per_split ? gc::ceil_div(a.c.K, a.k_per_split) : 1);
+    dim3 grid((unsigned)p.gx, gc::ceil_div(a.c.N, C::OCT), p.split ? p.slices : 1);
     const int epi = (a.c.bias || a.c.noise || a.c.act || a.c.residual) ? 2 : (a.c.so ? 1 : 0);
     if (epi == 2)      hipLaunchKernelGGL((convt_fused_bf16x3_kernel<WG_OC, WG_PX, WPX, TPW, 2>), grid, dim3(256), 0, s, a);
     else if (epi == 1) hipLaunchKernelGGL((convt_fused_bf16x3_kernel<WG_OC, WG_PX, WPX, TPW, 1>), grid, dim3(256), 0, s, a);
@@ -577,42 +569,64 @@ int launch_t(Bf16Args a, hipStream_t s, bool main_only = false) {
     return gc::check_launch("gc_conv2d_bf16x3_f32(fused transposed)");
 }
 
+template <int WG_OC, int WG_PX, int WPX, int TPW>
+void set_t(ConvPlan& p, ConvPath path) {
+    using C = TCfg<WG_OC, WG_PX, WPX, TPW>;
+    p.path = path;
+    p.t[0] = WG_OC; p.t[1] = WG_PX; p.t[2] = WPX; p.t[3] = TPW;
+    p.tile_h = C::TQH; p.tile_w = TPW; p.oct = C::OCT;
+}
+
 }  // namespace
 
 namespace gcconv {
 inline namespace GC_ARITH {
 
-// q-space is (H + 1) wide for a (2H + 1)-wide output: take the tile width that wastes fewer lanes
-int dispatch_t(const Bf16Args& a, hipStream_t s) {
-    const int qw = gc::ceil_div(a.c.out_w, 2);
-    const bool narrow = gc::ceil_div(qw, 16) * 16 < gc::ceil_div(qw, 32) * 32;
-#if GC_CTWS == 1
-    if (tws_eligible(a)) {
-        if (a.c.N % 64 != 0) return launch_tws<1, 32>(a, s);                 // 32 oc x 16 rows x 32 q-columns
-        return narrow ? launch_tws<2, 16>(a, s) : launch_tws<2, 32>(a, s);    // 64 oc x (16 x 16 | 8 x 32) q-pixels
-    }
-#endif
+void plan_t(const gc_conv_desc* d, const gc_conv_epilogue* ep, size_t room, ConvPlan& p) {
+    const int qh = gc::ceil_div(d->out_h, 2), qw = gc::ceil_div(d->out_w, 2);
     // <= 32 output channels: the layer is bound by its stores, and 32-column q-tiles write 256-byte runs per row instead of 128-byte
-    // ones (64 -> 32 @512^2: 254 -> 232 us) -- worth more than the 16 columns of lanes a 513-wide q-row wastes
-    if (a.c.N <= 32) return launch_t<1, 4, 2, 32>(a, s);
-    if (ct_edge_eligible(a)) {
+    // ones (64 -> 32 @512^2: 254 -> 232 us) -- worth more than the 16 columns of lanes a 513-wide q-row wastes.
+    // Otherwise: q-space is (H + 1) wide for a (2H + 1)-wide output, take the tile width that wastes fewer lanes
+    if (d->out_ch <= 32) set_t<1, 4, 2, 32>(p, ConvPath::CT);
+    else if (gc::ceil_div(qw, 16) * 16 < gc::ceil_div(qw, 32) * 32) set_t<2, 2, 2, 16>(p, ConvPath::CT);
+    else set_t<2, 2, 2, 32>(p, ConvPath::CT);
+    plan_tiles(p, qh, qw);
+    // split over K (round 5: 512 -> 512 @8^2 / @16^2 were 64 / 160 workgroups walking all 32 chunks: 90 us each whatever the plane): dense rows only
+    // (the finish pass writes dense rows), the 64-channel tiles only
+    if (GC_CT_SPLITK && d->out_ch > 32 && dense_output(d)) plan_split(p, d, room);
+    p.gx = (long long)p.tiles_x * p.tiles_y * d->batch;
+    if (p.split) return;
+#if GC_CTWS == 1
+    if (plan_tws(d, ep, p)) return;
+#endif
+    if (ct_edge_eligible(d, p)) {
+        // the fused kernel over the H x W main region, which its 4 x 32 q-tiles cover exactly
+        set_t<2, 2, 2, 32>(p, ConvPath::CT_EDGE);
+        plan_tiles(p, d->in_h, d->in_w);
+        p.gx = (long long)p.tiles_x * p.tiles_y * d->batch;
 #if GC_CTWS == 2
-        // round 6 experiment: the H x W main region on the wave-specialised kernel (its 8 x 32 q-tiles then cover the region exactly)
-        if (a.c.in_h % 8 == 0 && !(a.c.bias || a.c.noise || a.c.act || a.c.residual)) {
-            if (gc::probing()) return gc::probe_name("convt_bf16x3_ws_kernel<2,32>+edge|up2,down1,k3");
-            if (int rc = launch_tws<2, 32>(a, s, true)) return rc;
-            const dim3 grid((unsigned)(gc::ceil_div(a.c.in_w + 1, 32) + gc::ceil_div(a.c.in_h, 32)), (unsigned)(a.c.N / 64), (unsigned)a.c.B);
-            hipLaunchKernelGGL(convt_edge_bf16x3_kernel, grid, dim3(256), 0, s, a);
-            return gc::check_launch("gc_conv2d_bf16x3_f32(transposed ws, edge)");
+        // round 6 experiment: the main region on the wave-specialised kernel (its 8 x 32 q-tiles then cover the region exactly)
+        if (d->in_h % 8 == 0 && !(ep && (ep->bias || ep->noise || ep->activate || ep->residual))) {
+            set_tws<2, 32>(p, ConvPath::CTWS_EDGE);
+            plan_tiles(p, d->in_h, d->in_w);
+            plan_resident(p, d);
         }
 #endif
-        if (gc::probing()) return gc::probe_name("convt_fused_bf16x3_kernel<2,2,2,32>+edge|up2,down1,k3");
-        if (int rc = launch_t<2, 2, 2, 32>(a, s, true)) return rc;
-        const dim3 grid((unsigned)(gc::ceil_div(a.c.in_w + 1, 32) + gc::ceil_div(a.c.in_h, 32)), (unsigned)(a.c.N / 64), (unsigned)a.c.B);
-        hipLaunchKernelGGL(convt_edge_bf16x3_kernel, grid, dim3(256), 0, s, a);
-        return gc::check_launch("gc_conv2d_bf16x3_f32(transposed, edge)");
     }
-    return narrow ? launch_t<2, 2, 2, 16>(a, s) : launch_t<2, 2, 2, 32>(a, s);
+}
+
+int launch_t(const ConvPlan& p, const Bf16Args& a, hipStream_t s) {
+    int rc;
+#if GC_CTWS
+    if (p.path == ConvPath::CTWS || p.path == ConvPath::CTWS_EDGE) rc = launch_tws(p, a, s);
+    else
+#endif
+    if (p.t[0] == 1) rc = launch_t_inst<1, 4, 2, 32>(p, a, s);
+    else rc = p.t[3] == 32 ? launch_t_inst<2, 2, 2, 32>(p, a, s) : launch_t_inst<2, 2, 2, 16>(p, a, s);
+    if (rc || !p.edge()) return rc;
+    const dim3 grid((unsigned)(gc::ceil_div(a.c.in_w + 1, 32) + gc::ceil_div(a.c.in_h, 32)), (unsigned)(a.c.N / 64), (unsigned)a.c.B);
+    hipLaunchKernelGGL(convt_edge_bf16x3_kernel, grid, dim3(256), 0, s, a);
+    return gc::check_launch("gc_conv2d_bf16x3_f32(transposed, edge)");
 }
 
 }  // namespace GC_ARITH

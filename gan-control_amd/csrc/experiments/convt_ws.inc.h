@@ -325,33 +325,40 @@ __global__ __launch_bounds__(768) void convt_bf16x3_ws_kernel(Bf16Args a) {
 }
 
 template <int WOCB, int TPW>
-int launch_tws(Bf16Args a, hipStream_t s, bool main_only = false) {
-    using C = TWCfg<WOCB, TPW>;
-    const int qh = main_only ? a.c.in_h : gc::ceil_div(a.c.out_h, 2), qw = main_only ? a.c.in_w : gc::ceil_div(a.c.out_w, 2);     // main_only: the H x W region (convt_edge_bf16x3_kernel does the rest)
-    a.c.tiles_y = gc::ceil_div(qh, C::TQH);
-    a.c.tiles_x = gc::ceil_div(qw, TPW);
-    const int tiles = a.c.tiles_x * a.c.tiles_y, ocb = a.c.N / C::OCT;
-    const long long wgs = (long long)tiles * a.c.B * ocb;
-    a.tpb = (int)std::min<long long>(std::max<long long>((wgs + GC_WS_SLOTS - 1) / GC_WS_SLOTS, 1), tiles);
-    a.groups = gc::ceil_div(tiles, a.tpb);
-    const long long gx = (long long)a.groups * a.c.B;
-    if (gx > 2147483647LL) return gc::fail(GC_ERR_UNSUPPORTED, "gc_conv2d_bf16x3_f32: grid too large");
-    if (gc::probing()) return gc::probe_name("convt_bf16x3_ws_kernel<%d,%d>|up2,down1,k3", WOCB, TPW);
-    const dim3 grid((unsigned)gx, ocb);
+int launch_tws_inst(const ConvPlan& p, const Bf16Args& a, hipStream_t s) {
+    const dim3 grid((unsigned)p.gx, a.c.N / TWCfg<WOCB, TPW>::OCT);
     if (a.c.so) hipLaunchKernelGGL((convt_bf16x3_ws_kernel<WOCB, TPW, 1>), grid, dim3(768), 0, s, a);
     else        hipLaunchKernelGGL((convt_bf16x3_ws_kernel<WOCB, TPW, 0>), grid, dim3(768), 0, s, a);
     return gc::check_launch("gc_conv2d_bf16x3_f32(transposed, ws)");
 }
 
-// the transposed layers the wave-specialised kernel takes: whole 16-channel chunks, whole 32- / 64-channel output blocks, enough chunks
-// per item sequence to amortise its start-up, enough tiles to give most CUs a workgroup
-inline bool tws_eligible(const Bf16Args& a) {
-    const ConvArgs& c = a.c;
-    if (a.k_per_split || c.K % KCB != 0 || c.K < 32 || c.N % 32 != 0) return false;
-    if (c.bias || c.noise || c.act || c.residual) return false;       // the full fused epilogue (no caller in the training step) stays on the one-role kernel
-    const int qh = gc::ceil_div(c.out_h, 2), qw = gc::ceil_div(c.out_w, 2);
+inline int launch_tws(const ConvPlan& p, const Bf16Args& a, hipStream_t s) {
+    if (p.t[0] == 1) return launch_tws_inst<1, 32>(p, a, s);                                                   // 32 oc x 16 rows x 32 q-columns
+    return p.t[1] == 16 ? launch_tws_inst<2, 16>(p, a, s) : launch_tws_inst<2, 32>(p, a, s);                   // 64 oc x (16 x 16 | 8 x 32) q-pixels
+}
+
+template <int WOCB, int TPW>
+void set_tws(ConvPlan& p, ConvPath path) {
+    using C = TWCfg<WOCB, TPW>;
+    p.path = path;
+    p.t[0] = WOCB; p.t[1] = TPW; p.t[2] = p.t[3] = 0;
+    p.tile_h = C::TQH; p.tile_w = TPW; p.oct = C::OCT;
+}
+
+// the transposed layers the wave-specialised kernel takes (GC_CTWS = 1; p: the unsplit plan of the one-role kernel): whole 16-channel chunks, whole
+// 32- / 64-channel output blocks, enough chunks per item sequence to amortise its start-up, enough tiles to give most CUs a workgroup
+inline bool plan_tws(const gc_conv_desc* d, const gc_conv_epilogue* ep, ConvPlan& p) {
+    if (d->in_ch % KCB != 0 || d->in_ch < 32 || d->out_ch % 32 != 0) return false;
+    if (ep && (ep->bias || ep->noise || ep->activate || ep->residual)) return false;       // the full fused epilogue (no caller in the training step) stays on the one-role kernel
+    const int qh = gc::ceil_div(d->out_h, 2), qw = gc::ceil_div(d->out_w, 2);
     if (qw < 32 || qh < 16) return false;
-    const int oct = c.N % 64 == 0 ? 64 : 32;
-    const long long wgs = (long long)gc::ceil_div(qw, 32) * gc::ceil_div(qh, oct == 64 ? 8 : 16) * c.B * (c.N / oct);
-    return wgs >= 192;
+    const int oct = d->out_ch % 64 == 0 ? 64 : 32;
+    const long long wgs = (long long)gc::ceil_div(qw, 32) * gc::ceil_div(qh, oct == 64 ? TWCfg<2, 32>::TQH : TWCfg<1, 32>::TQH) * d->batch * (d->out_ch / oct);
+    if (wgs < 192) return false;
+    if (oct == 32) set_tws<1, 32>(p, ConvPath::CTWS);
+    else if (p.t[3] == 16) set_tws<2, 16>(p, ConvPath::CTWS);      // the narrow q-tiles where the one-role kernel takes them
+    else set_tws<2, 32>(p, ConvPath::CTWS);
+    plan_tiles(p, qh, qw);
+    plan_resident(p, d);
+    return true;
 }

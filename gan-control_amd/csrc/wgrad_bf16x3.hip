@@ -865,13 +865,25 @@ __global__ __launch_bounds__(256, (TR == 1 || WK == 1) ? 2 : 1) void wgrad_bf16x
     }
 }
 
-struct WgPlan { int small, ct, kt, tr, splits, tiles_per_split, tiles_x, tiles_y; };
+struct WgPlan { int small, ct, kt, tr, splits, tiles_per_split, tiles_x, tiles_y, bands; };      // bands > 0: wgrad_bf16x3_ws2_kernel with that many 16-row bands
 #ifndef GC_WG_S2_N128
 #define GC_WG_S2_N128 1      // stride-2 weight gradients with N % 128 == 0 and K % 32 == 0 (K >= 64) on 32k x 128n tiles (wgrad_bf16x3_s2_kernel<1, KS, 1, 4>); 0: 64k x 64n
 #endif
 #ifndef GC_WG_SPLIT_TARGET
 #define GC_WG_SPLIT_TARGET 512      // workgroups a weight-gradient launch aims for (pixel splits x channel tiles)
 #endif
+
+// the shapes of the wave-specialised kernel (wgrad_bf16x3_ws2_kernel): 3 x 3 "same" convolutions with whole 64-channel blocks on both sides, rows of >= 32
+// pixels, whole 16-row strips ...
+inline bool ws2_shape(const gc_conv_desc* d, bool small) {
+    return GC_WG_WS && d->down == 1 && d->kh == 3 && !small && d->in_ch % 64 == 0 && d->out_ch % 64 == 0 && d->pad_x == 1 && d->pad_y == 1 &&
+           d->out_w >= 32 && d->out_h == d->in_h && d->out_w == d->in_w && d->out_h % 16 == 0;
+}
+// ... and of those the launches that leave every split at least two strips: `per` splits share a pool of `pool` strips per row band.  The bands, else 0.
+inline int ws2_bands(const gc_conv_desc* d, long long pool, int per) {
+    const int bands = d->out_h / 16;
+    return pool * bands >= 2LL * per ? bands : 0;
+}
 
 // 64k x 64n tiles (2 rows per pixel tile) when both channel counts reach 64, else 32k x 32n tiles with the four
 // waves splitting the pixel steps of a 4-row tile
@@ -890,24 +902,24 @@ WgPlan plan_wg(const gc_conv_desc* d) {
     pl.tiles_y = gc::ceil_div(d->out_h, pl.tr);
     const int total = pl.tiles_x * pl.tiles_y * d->batch;
     const int ctiles = gc::ceil_div(d->in_ch, pl.kt) * gc::ceil_div(d->out_ch, pl.ct);
-    // one workgroup per CU is resident (512 registers per lane): two rounds -- except on the shapes wgrad_bf16x3_ws2_kernel takes (see wgrad_launch): its
+    // one workgroup per CU is resident (512 registers per lane): two rounds -- except on the shapes wgrad_bf16x3_ws2_kernel takes: its
     // 16-wave workgroups run longer per strip and ONE full round of 256 measured 3..12 % faster at every channel count (same box, B = 2 / 4 / 8,
     // profiles/wg_ab_r05.log: 512 ch @64^2 232 -> 220 us, 256 @128^2 222 -> 209, 128 @256^2 235 -> 221, 64 @512^2 251 -> 231 at B = 4); everything else
     // is 20..50 % slower with 256
-    const bool ws2_shape = GC_WG_WS && d->down == 1 && d->kh == 3 && !pl.small && d->in_ch % 64 == 0 && d->out_ch % 64 == 0 && d->pad_x == 1 && d->pad_y == 1 &&
-                           d->out_w >= 32 && d->out_h == d->in_h && d->out_w == d->in_w && d->out_h % 16 == 0;
+    const bool ws2 = ws2_shape(d, pl.small);
+    const long long pool = (long long)pl.tiles_x * d->batch;         // every split draws on the strips of the whole batch
     int want = gc::ceil_div(GC_WG_SPLIT_TARGET, ctiles);
-    if (ws2_shape) {
-        // ... provided that kernel really takes the launch with the halved split count (wgrad_launch: at least two 16-row strips per split);
-        // 512 -> 512 @32^2 at B = 2 does not, and the one-role kernel with half the splits is 9 % slower
+    if (ws2) {
+        // ... provided that kernel really takes the launch with the halved split count; 512 -> 512 @32^2 at B = 2 does not, and the one-role kernel
+        // with half the splits is 9 % slower
         const int half = std::max(1, std::min(gc::ceil_div(GC_WG_SPLIT_TARGET / 2, ctiles), total));
-        const int splits = gc::ceil_div(total, gc::ceil_div(total, half));
-        if ((long long)pl.tiles_x * d->batch * (d->out_h / 16) >= 2LL * splits) want = half;
+        if (ws2_bands(d, pool, gc::ceil_div(total, gc::ceil_div(total, half)))) want = half;
     }
     if (want > total) want = total;
     if (want < 1) want = 1;
     pl.tiles_per_split = gc::ceil_div(total, want);
     pl.splits = gc::ceil_div(total, pl.tiles_per_split);
+    pl.bands = ws2 ? ws2_bands(d, pool, pl.splits) : 0;
     return pl;
 }
 }  // namespace
@@ -953,6 +965,7 @@ WgPlan plan_wg_samples(const gc_conv_desc* d) {
     spb = std::max(1, std::min(spb, per_sample));
     pl.tiles_per_split = gc::ceil_div(per_sample, spb);
     pl.splits = spb * d->batch;
+    pl.bands = ws2_shape(d, pl.small) ? ws2_bands(d, pl.tiles_x, spb) : 0;        // a sample's splits share the strips of that sample
     return pl;
 }
 
@@ -977,24 +990,10 @@ int wgrad_launch(const gc_conv_desc* d, const float* x, const float* dy, const f
         return gc::probe_name("%s|down%d,k%d%s|plan:splits=%d,tiles_per_split=%d%s%s", kernel, d->down, d->kh, dw_samples ? "|samples" : "",
                               pl.splits, pl.tiles_per_split, extra, direct ? ",direct" : "");
     };
-#if GC_WG_WS
-    // the wave-specialised kernel: 3 x 3 "same" convolutions with whole 64-channel blocks on both sides; strips of rb rows, at least two per split
-    if (d->down == 1 && d->kh == 3 && !pl.small && d->in_ch % 64 == 0 && d->out_ch % 64 == 0 && d->pad_x == 1 && d->pad_y == 1 && d->out_w >= 32 &&
-        d->out_h == d->in_h && d->out_w == d->in_w) {
-        const int per = dw_samples ? pl.splits / d->batch : pl.splits;                     // splits that share one pool of strips
-        const long long pool = (long long)pl.tiles_x * (dw_samples ? 1 : d->batch);          // ... strips per row band in that pool
-        const int rb = (d->out_h % 16 == 0 && pool * (d->out_h / 16) >= 2LL * per) ? 16 : 0;
-        if (rb) {
-            if (gc::probing()) return probe("wgrad_bf16x3_ws2_kernel", d->out_h / rb);
-            hipLaunchKernelGGL(wgrad_bf16x3_ws2_kernel, grid, dim3(1024), 0, s, a, d->out_h / rb);
-            int rc = gc::check_launch(who);
-            if (rc || direct) return rc;
-            if (dw_samples) return launch_wgrad_reduce_samples(static_cast<const float*>(workspace), dw, dw_samples, count, d->batch, pl.splits / d->batch, s);
-            return launch_wgrad_reduce(static_cast<const float*>(workspace), dw, count, pl.splits, s);
-        }
-    }
-#endif
-    if (d->down == 2) {
+    if (pl.bands) {
+        if (gc::probing()) return probe("wgrad_bf16x3_ws2_kernel", pl.bands);
+        hipLaunchKernelGGL(wgrad_bf16x3_ws2_kernel, grid, dim3(1024), 0, s, a, pl.bands);
+    } else if (d->down == 2) {
         if (pl.ct == 128) {
             if (gc::probing()) return probe("wgrad_bf16x3_s2_kernel<1,%d,1,4>", 0);
             if (d->kh == 3) hipLaunchKernelGGL((wgrad_bf16x3_s2_kernel<1, 3, 1, 4>), grid, dim3(256), 0, s, a);

@@ -281,3 +281,28 @@ def test_every_step_conv_variant_has_a_kernel_case():
         oh, ow = _out(h, k, up, down, pad), _out(w, k, up, down, pad)
         cases.add(conv_variant(ConvGeom(k, k, up, down, pad, pad, oh, ow), N, b, K, 'bf16x3', (h, w)))
     assert step <= cases, sorted(step - cases)
+
+
+@pytest.mark.parametrize('out_h,out_w,prefix', [(40, 33, 'conv_bf16x3_kernel<1,4,2,1>|up1,down2'), (33, 33, 'conv_s2ws_bf16x3_kernel<1>'),
+                                                (33, 40, 'conv_bf16x3_kernel<1,4,2,1>|up1,down2')])
+def test_unmasked_stride2_kernel_takes_only_outputs_that_read_inside_the_plane(out_h, out_w, prefix):
+    """conv_s2ws_bf16x3_kernel masks nothing: a descriptor whose output extent exceeds (in - 3) / 2 + 1 on either axis (legal: those pixels read zeros) stays
+    on the masked one-role kernel.  67 x 67 -> 33 x 33 is the consistent geometry; 20 samples reach the kernel's 192-workgroup threshold."""
+    geom = ConvGeom(3, 3, 1, 2, 0, 0, out_h, out_w)
+    assert conv_variant(geom, 64, 20, 32, 'bf16x3', (67, 67)).startswith(prefix)
+
+
+# ---- the whole decision table (tools/dispatch_table.py): every probe and every size / pitch query over a fixed descriptor grid, frozen as a digest ----
+
+def test_dispatch_table_matches_the_frozen_digest():
+    """Host-side dispatch work must not move a decision: the digest of the table equals tests/golden/dispatch_table.json.  A deliberate change regenerates
+    the file (`python tools/dispatch_table.py --write`) and says in its commit which rows moved."""
+    import json
+    sys.path.insert(0, os.path.join(REPO, 'tools'))
+    import dispatch_table
+    with open(dispatch_table.GOLDEN) as f:
+        frozen = json.load(f)
+    now = dispatch_table.digest()
+    moved = sorted(g for g in set(frozen) | set(now) if frozen.get(g) != now.get(g))
+    assert not moved, ('these (geometry | column) groups of the decision table moved: %s -- run `python tools/dispatch_table.py --dump` on the parent build and '
+                       'on this one and diff the two outputs to see the rows' % moved)

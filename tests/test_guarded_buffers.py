@@ -825,7 +825,7 @@ SHIFT_EXCEPTION_CAP = 10          # per cent of CASES, both lists together; more
 # ---- the range check of a raw buffer access on gfx950: is the scalar offset part of it? -------------------------------------------------------------
 # No forward kernel MULTIPLIES a value it loaded through a nonzero scalar offset from beyond its descriptor: conv_bf16x3_kernel and
 # convt_fused_bf16x3_kernel clamp the channel to K - 1 (conv_bf16x3.hip:227, convt_bf16x3.hip:143; the weights and s_si are zero past K), the
-# wave-specialised kernels take K % 16 == 0 only (ws_eligible, s2ws_eligible), and what a 16-byte load fetches past a row end is selected away
+# wave-specialised kernels take K % 16 == 0 only (plan_ws, plan_s2ws), and what a 16-byte load fetches past a row end is selected away
 # (`i < inrow`).  The weight-gradient kernels select too (unit8, x_store, y_store).  So no NaN behind an input can tell the two rules apart, for any
 # of the load sites.  The STORES of conv_bf16x3_kernel do (conv_bf16x3.hip:386): an output channel goes into the scalar offset, `ocs * oplane`, and the
 # lane offset is the pixel plus `4 * hi` planes.  In the case below N = 20 and the channel tile is 32, so every pixel is stored for the channels 20 ..
@@ -1062,6 +1062,27 @@ def test_scalar_offset_rule_case_stores_phantom_channels_into_its_guard():
     assert mode == 'bf16x3' and name.startswith('conv_bf16x3_kernel<1,4,1,') and K % 32 and N % 32 == 20 and b >= 2
     assert 0 < (32 - N) * g.out_h * g.out_w * 4 <= ga.MIN_GUARD
     assert SCALAR_OFFSET_RULE_CASE in {cs.name for cs in CASES}
+
+
+@pytest.mark.gpu
+def test_stride2_rows_past_the_input_plane_read_zeros(hip):
+    """A legal stride-2 descriptor whose output extent exceeds what the input implies (67 x 67 -> 40 x 33: rows 33 .. 39 read input rows 66 .. 80) runs
+    on the masked conv_bf16x3_kernel, not on conv_s2ws_bf16x3_kernel, which masks nothing and would read the next channel's rows (and, placed as here,
+    the NaN words around the tensor): the result is the fp64 convolution of the input zero-extended to 81 rows, within the split-bf16 bound."""
+    b, K, N, h, w = 20, 32, 64, 67, 67
+    geom = ConvGeom(3, 3, 1, 2, 0, 0, 40, 33)
+    gen = _gen('oversized-stride2')
+    x, wt = torch.randn(b, K, h, w, generator=gen), torch.randn(3, 3, K, N, generator=gen)
+    si, so = torch.randn(b, K, generator=gen), torch.rand(b, N, generator=gen) + 0.5
+    ref = EmulatedBackend().conv2d(x.double(), wt.double(), si.double(), so.double(), geom)          # (pads the input with zeros up to the extent the output reads)
+    prev, hip.conv_mode = hip.conv_mode, 'bf16x3'
+    try:
+        out = hip.conv2d(ga.hostile(x.to(DEV), 'nan'), wt.to(DEV), si.to(DEV), so.to(DEV), geom)
+    finally:
+        hip.conv_mode = prev
+    err = rel_err(out, ref)
+    print('oversized stride-2 descriptor: %d non-finite outputs, %.3g against fp64 (bound %.3g)' % (int((~torch.isfinite(out)).sum()), err, _TOL['bf16x3']))
+    assert err < _TOL['bf16x3']
 
 
 def launching_entries():
