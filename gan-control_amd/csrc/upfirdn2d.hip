@@ -34,25 +34,14 @@ struct FirEpilogue {
     const float* pro_ref; const float* pro_noise; float* pro_psum; float* pro_pdot; float ppos, pneg;
 };
 
-// GC_FIR_NT vertically consecutive tiles per workgroup in one software pipeline (the 16-byte loads of tile t + 1 issued before the
-// arithmetic and the stores of tile t, committed to LDS after them).  Measured with 4 tiles per workgroup (round 3, same-box A/B,
-// tools/kbench.py): SLOWER -- [4, 32, 1025^2] 212 -> 252 us (5.07 -> 4.26 TB/s), [4, 64, 513^2] 111 -> 128 us, [4, 128, 257^2] 54 -> 64 us: the
-// eight workgroups a CU holds already overlap each other's load / compute / store phases, and a quarter of the workgroups with two more
-// barriers per tile only lengthens the tail.  One tile per workgroup stays the default.
-#ifndef GC_FIR_NT
-#define GC_FIR_NT 1
-#endif
+// Tiles per workgroup.  The tile loop at the end of fir44_tile_kernel is the software pipeline of a multi-tile form (the 16-byte loads of tile
+// t + 1 issued before the arithmetic and the stores of tile t, committed to LDS after them) that measured slower at four tiles and is retired
+// ("Tried and rejected").  One tile is the only depth: the prologue sums are written once per workgroup, and the host grid has one
+// workgroup per tile.  The loop keeps its source form because the code generator follows it (profiles/fir_plan.md).
+constexpr int FIR_NT = 1;
 
-#ifndef GC_FIR_OCC
-#define GC_FIR_OCC 0          // dev knob: > 0 = waves per SIMD the tile kernel is compiled for (register cap 512 / OCC)
-#endif
-#if GC_FIR_OCC > 0
-#define GC_FIR_BOUNDS __launch_bounds__(256, GC_FIR_OCC)
-#else
-#define GC_FIR_BOUNDS __launch_bounds__(256)
-#endif
 template <bool VEC, int EPI, bool PRO = false>
-__global__ GC_FIR_BOUNDS void fir44_tile_kernel(
+__global__ __launch_bounds__(256) void fir44_tile_kernel(
     const float* __restrict__ x, const float* __restrict__ taps, float* __restrict__ y,
     int in_h, int in_w, int out_h, int out_w, int pad_x0, int pad_y0, int flip, FirEpilogue ep, int in_pitch, int out_pitch) {
     __shared__ __attribute__((aligned(16))) float patch[PH * PITCH];
@@ -92,7 +81,6 @@ __global__ GC_FIR_BOUNDS void fir44_tile_kernel(
         }
         return v;
     };
-    static_assert(!PRO || GC_FIR_NT == 1, "the prologue sums are written once per workgroup");
     float ps = 0.f, pd = 0.f;                                // PRO: this lane's share of the tile's sums
     const float* refp = PRO ? ep.pro_ref + plane * (size_t)in_h * in_w : nullptr;
     const float* nzp = (PRO && ep.pro_noise) ? ep.pro_noise + (plane / ep.channels) * (size_t)in_h * in_w : nullptr;
@@ -134,9 +122,9 @@ __global__ GC_FIR_BOUNDS void fir44_tile_kernel(
 
     const int cg = tid & 31, rg = tid >> 5;   // 32 column groups x 8 row groups of 4x4 outputs
     const int ox = ox0 + cg * 4;
-    const int ty0 = blockIdx.y * GC_FIR_NT;
+    const int ty0 = blockIdx.y * FIR_NT;
     const int tiles_y = (out_h + TH - 1) / TH;
-    const int nt = min(GC_FIR_NT, tiles_y - ty0);
+    const int nt = min(FIR_NT, tiles_y - ty0);
     fetch(ty0 * TH);
     __shared__ float red[8];
     if (PRO) {
@@ -575,23 +563,43 @@ __global__ __launch_bounds__(256) void firK_tile_kernel(
         if (ox0 + tx + i < out_w) yp[(size_t)oy * out_w + ox0 + tx + i] = acc[i];
 }
 
-template <int K>
-int launch_firK(const float* x, const float* taps, float* y, int planes, int in_h, int in_w, int out_h, int out_w,
-                int up, int down, int pad_x0, int pad_y0, int flip, hipStream_t s) {
-    using C = FirKCfg<K, 1, 1>;
-    dim3 grid(gc::ceil_div(out_w, C::TW), gc::ceil_div(out_h, C::TH), planes);
-    if (up == 2 && down == 1)
-        hipLaunchKernelGGL((firK_tile_kernel<K, 2, 1>), grid, dim3(256), 0, s, x, taps, y, in_h, in_w, out_h, out_w, pad_x0, pad_y0, flip);
-    else if (up == 1 && down == 2)
-        hipLaunchKernelGGL((firK_tile_kernel<K, 1, 2>), grid, dim3(256), 0, s, x, taps, y, in_h, in_w, out_h, out_w, pad_x0, pad_y0, flip);
-    else
-        hipLaunchKernelGGL((firK_tile_kernel<K, 1, 1>), grid, dim3(256), 0, s, x, taps, y, in_h, in_w, out_h, out_w, pad_x0, pad_y0, flip);
-    return gc::check_launch("gc_upfirdn2d_f32(firK_tile)");
+// ---------------------------------------------------------------------------------------------------------
+// The launch decision, made once.  plan_fir is the only place that says which kernel takes a shape; the launcher, the tile-count query
+// (gc_upfirdn2d_actbwd_tiles) and the no-launch probe (gc_upfirdn2d_variant_name: what the Python side routes and times by) all read it.
+enum FirPath { FIR_NONE, FIR_TILE, FIR_SMALL, FIR_DOWN2, FIR_UP2, FIR_K12, FIR_GENERIC };
+
+struct FirPlan {
+    FirPath path; dim3 grid; int ppw;       // ppw: planes per workgroup of fir44_small_kernel
+    const char* name; int rc;               // what the path is reported as; GC_OK, or why there is no path (the text is in gc_last_error)
+};
+
+// every tiled kernel puts one plane on blockIdx.z
+inline dim3 tiles(int out_h, int out_w, int th, int tw, int planes) { return dim3(gc::ceil_div(out_w, tw), gc::ceil_div(out_h, th), planes); }
+
+FirPlan plan_fir(int kh, int kw, int up_x, int up_y, int down_x, int down_y, int planes, int out_h, int out_w) {
+    if (planes < 0 || kh <= 0 || kw <= 0 || up_x <= 0 || up_y <= 0 || down_x <= 0 || down_y <= 0)
+        return {FIR_NONE, dim3(), 0, "", gc::fail(GC_ERR_BAD_ARG, "gc_upfirdn2d_f32: non-positive extent or factor")};
+    if (out_h <= 0 || out_w <= 0) return {FIR_NONE, dim3(), 0, "", gc::fail(GC_ERR_BAD_ARG, "gc_upfirdn2d_f32: empty output (%d x %d)", out_h, out_w)};
+    const bool k44 = kh == 4 && kw == 4, square = up_x == up_y && down_x == down_y;
+    const bool unit = square && up_x == 1 && down_x == 1;
+    const bool grid_z = planes <= 65535;                                    // the limit of gridDim.z
+    if (k44 && unit && grid_z && out_w >= 64 && out_h >= 16) return {FIR_TILE, tiles(out_h, out_w, TH, TW, planes), 0, "fir44_tile_kernel", GC_OK};
+    const int64_t lp = (int64_t)(out_h + 3) * (out_w + 3);                  // the zero-padded plane fir44_small_kernel stages
+    if (k44 && unit && lp <= SMALL_PLANE_MAX) {
+        const int ppw = std::max(1, std::min(SMALL_LDS_FLOATS / (int)lp, 1024 / std::max(1, out_h * out_w) + 1));
+        return {FIR_SMALL, dim3(gc::ceil_div(planes, ppw)), ppw, "fir44_small_kernel", GC_OK};
+    }
+    const bool tiled = square && grid_z && out_w >= 32 && out_h >= 8;       // planes worth a tile of the up / down kernels
+    if (k44 && tiled && up_x == 1 && down_x == 2) return {FIR_DOWN2, tiles(out_h, out_w, D_TH, D_TW, planes), 0, "fir44_down2_kernel", GC_OK};
+    if (k44 && tiled && up_x == 2 && down_x == 1) return {FIR_UP2, tiles(out_h, out_w, U_TH, U_TW, planes), 0, "fir44_up2_kernel", GC_OK};
+    // 12 x 12 taps (sym6 x sym6) with (up, down) in {(2, 1), (1, 2), (1, 1)}: the ADA anti-aliasing passes
+    using C12 = FirKCfg<12, 1, 1>;
+    if (kh == 12 && kw == 12 && tiled && up_x * down_x <= 2) return {FIR_K12, tiles(out_h, out_w, C12::TH, C12::TW, planes), 0, "firK_tile_kernel<12>", GC_OK};
+    if (kh * kw > MAX_GENERIC_TAPS)
+        return {FIR_NONE, dim3(), 0, "", gc::fail(GC_ERR_UNSUPPORTED, "gc_upfirdn2d_f32: %d x %d taps exceed %d", kh, kw, MAX_GENERIC_TAPS)};
+    const size_t total = (size_t)planes * out_h * out_w;
+    return {FIR_GENERIC, dim3((int)std::min<size_t>((total + 255) / 256, 256 * 16)), 0, "upfirdn2d_generic_kernel", GC_OK};
 }
-
-}  // namespace
-
-namespace {
 
 int upfirdn2d_impl(const float* x, const float* taps, float* y,
                    int planes, int in_h, int in_w, int out_h, int out_w,
@@ -602,72 +610,59 @@ int upfirdn2d_impl(const float* x, const float* taps, float* y,
     if (out_pitch < out_w) return gc::fail(GC_ERR_BAD_ARG, "gc_upfirdn2d_f32: output pitch %d < width %d", out_pitch, out_w);
     if (in_pitch < in_w) return gc::fail(GC_ERR_BAD_ARG, "gc_upfirdn2d_f32: input pitch %d < width %d", in_pitch, in_w);
     if (!x || !taps || !y) return gc::fail(GC_ERR_BAD_ARG, "gc_upfirdn2d_f32: null pointer");
-    if (planes < 0 || in_h <= 0 || in_w <= 0 || kh <= 0 || kw <= 0 || up_x <= 0 || up_y <= 0 || down_x <= 0 || down_y <= 0)
-        return gc::fail(GC_ERR_BAD_ARG, "gc_upfirdn2d_f32: non-positive extent or factor");
-    if (out_h <= 0 || out_w <= 0) return gc::fail(GC_ERR_BAD_ARG, "gc_upfirdn2d_f32: empty output (%d x %d)", out_h, out_w);
+    if (in_h <= 0 || in_w <= 0) return gc::fail(GC_ERR_BAD_ARG, "gc_upfirdn2d_f32: non-positive extent or factor");
+    const FirPlan p = plan_fir(kh, kw, up_x, up_y, down_x, down_y, planes, out_h, out_w);
+    if (p.rc == GC_ERR_BAD_ARG) return p.rc;
     if (planes == 0) return GC_OK;
+    if (p.path != FIR_TILE && (ep || in_pitch != in_w || out_pitch != out_w))
+        return gc::fail(GC_ERR_UNSUPPORTED, "gc_upfirdn2d_f32: a fused epilogue and pitched rows need the 4x4, up = down = 1 tile kernel (planes >= 64 x 16, at most 65535 of them)");
+    if (p.path == FIR_NONE) return p.rc;
     hipStream_t s = (hipStream_t)stream;
-    const bool fast = up_x == 1 && up_y == 1 && down_x == 1 && down_y == 1 && kh == 4 && kw == 4 &&
-                      out_w >= 64 && out_h >= 16 && planes <= 65535;
-    if (ep && !fast) return gc::fail(GC_ERR_UNSUPPORTED, "gc_upfirdn2d_act_f32: the fused epilogue needs the 4x4, up = down = 1 tile kernel (planes >= 64 x 16)");
-    if ((in_pitch != in_w || out_pitch != out_w) && !fast) return gc::fail(GC_ERR_UNSUPPORTED, "gc_upfirdn2d_pitched_f32: a pitched input needs the 4x4, up = down = 1 tile kernel (planes >= 64 x 16)");
-    if (fast) {
-        dim3 grid(gc::ceil_div(out_w, TW), gc::ceil_div(gc::ceil_div(out_h, TH), GC_FIR_NT), planes);
-        const bool vec = (out_pitch % 4 == 0) && ((reinterpret_cast<uintptr_t>(y) & 15) == 0);      // rows start on 16-byte boundaries
+    // 16-byte stores want rows that start on 16-byte boundaries: the one choice that needs the output pointer (only the tile kernel takes a pitch)
+    const bool vec = (out_pitch % 4 == 0) && ((reinterpret_cast<uintptr_t>(y) & 15) == 0);
+    auto launch = [&](auto kernel, auto... rest) { hipLaunchKernelGGL(kernel, p.grid, dim3(256), 0, s, x, taps, y, rest...); };
+    switch (p.path) {
+    case FIR_TILE: {
+        // [epilogue kind][16-byte stores first]
+        using Kernel = decltype(&fir44_tile_kernel<true, 0>);
+        static constexpr Kernel kernels[4][2] = {{fir44_tile_kernel<true, 0, true>, fir44_tile_kernel<false, 0, true>}, {fir44_tile_kernel<true, 2>, fir44_tile_kernel<false, 2>},
+                                                 {fir44_tile_kernel<true, 1>, fir44_tile_kernel<false, 1>}, {fir44_tile_kernel<true, 0>, fir44_tile_kernel<false, 0>}};
         const FirEpilogue none{nullptr, nullptr, nullptr, 1.f, 1.f, 1, nullptr, 1.f, 1.f, nullptr, nullptr, nullptr, nullptr, 1.f, 1.f};
-        if (ep && ep->pro_ref) {
-            if (in_pitch != in_w) return gc::fail(GC_ERR_UNSUPPORTED, "gc_upfirdn2d_actbwd_f32: the gradient must have dense rows");
-            if (vec) hipLaunchKernelGGL((fir44_tile_kernel<true, 0, true>), grid, dim3(256), 0, s, x, taps, y, in_h, in_w, out_h, out_w, pad_x0, pad_y0, flip_taps, *ep, in_pitch, out_pitch);
-            else     hipLaunchKernelGGL((fir44_tile_kernel<false, 0, true>), grid, dim3(256), 0, s, x, taps, y, in_h, in_w, out_h, out_w, pad_x0, pad_y0, flip_taps, *ep, in_pitch, out_pitch);
-            return gc::check_launch("gc_upfirdn2d_actbwd_f32");
-        }
-#define GC_FIR(V, E) hipLaunchKernelGGL((fir44_tile_kernel<V, E>), grid, dim3(256), 0, s, x, taps, y, in_h, in_w, out_h, out_w, pad_x0, pad_y0, flip_taps, ep ? *ep : none, in_pitch, out_pitch)
-        if (ep && ep->mask_ref) { if (vec) GC_FIR(true, 2); else GC_FIR(false, 2); }
-        else if (ep) { if (vec) GC_FIR(true, 1); else GC_FIR(false, 1); }
-        else    { if (vec) GC_FIR(true, 0); else GC_FIR(false, 0); }
-#undef GC_FIR
-        return gc::check_launch("gc_upfirdn2d_f32(fir44_tile)");
+        const int kind = !ep ? 3 : ep->pro_ref ? 0 : ep->mask_ref ? 1 : 2;
+        if (kind == 0 && in_pitch != in_w) return gc::fail(GC_ERR_UNSUPPORTED, "gc_upfirdn2d_actbwd_f32: the gradient must have dense rows");
+        launch(kernels[kind][!vec], in_h, in_w, out_h, out_w, pad_x0, pad_y0, flip_taps, ep ? *ep : none, in_pitch, out_pitch);
+        break;
     }
-    if (kh == 4 && kw == 4 && up_x == 1 && up_y == 1 && down_x == 1 && down_y == 1 && (out_h + 3) * (out_w + 3) <= SMALL_PLANE_MAX) {
-        const int ppw = std::max(1, std::min(SMALL_LDS_FLOATS / ((out_h + 3) * (out_w + 3)), 1024 / std::max(1, out_h * out_w) + 1));
-        hipLaunchKernelGGL(fir44_small_kernel, dim3(gc::ceil_div(planes, ppw)), dim3(256), 0, s, x, taps, y, planes, in_h, in_w, out_h, out_w,
-                           pad_x0, pad_y0, flip_taps, ppw);
-        return gc::check_launch("gc_upfirdn2d_f32(fir44_small)");
+    case FIR_SMALL: launch(fir44_small_kernel, planes, in_h, in_w, out_h, out_w, pad_x0, pad_y0, flip_taps, p.ppw); break;
+    case FIR_DOWN2: launch(vec ? fir44_down2_kernel<true> : fir44_down2_kernel<false>, in_h, in_w, out_h, out_w, pad_x0, pad_y0, flip_taps); break;
+    case FIR_UP2: {
+        // [EY][EX][16-byte stores first]; (EY, EX): parity of (tile origin - pad), tile origins are multiples of 4
+        using Kernel = decltype(&fir44_up2_kernel<0, 0, true>);
+        static constexpr Kernel kernels[2][2][2] = {{{fir44_up2_kernel<0, 0, true>, fir44_up2_kernel<0, 0, false>}, {fir44_up2_kernel<0, 1, true>, fir44_up2_kernel<0, 1, false>}},
+                                                    {{fir44_up2_kernel<1, 0, true>, fir44_up2_kernel<1, 0, false>}, {fir44_up2_kernel<1, 1, true>, fir44_up2_kernel<1, 1, false>}}};
+        launch(kernels[pad_y0 & 1][pad_x0 & 1][!vec], in_h, in_w, out_h, out_w, pad_x0, pad_y0, flip_taps);
+        break;
     }
-    const bool square44 = kh == 4 && kw == 4 && up_x == up_y && down_x == down_y && planes <= 65535 && out_w >= 32 && out_h >= 8;
-    const bool vec_ok = (out_w % 4 == 0) && ((reinterpret_cast<uintptr_t>(y) & 15) == 0);
-    if (square44 && up_x == 1 && down_x == 2) {
-        dim3 grid(gc::ceil_div(out_w, D_TW), gc::ceil_div(out_h, D_TH), planes);
-        if (vec_ok)
-            hipLaunchKernelGGL(fir44_down2_kernel<true>, grid, dim3(256), 0, s, x, taps, y, in_h, in_w, out_h, out_w, pad_x0, pad_y0, flip_taps);
-        else
-            hipLaunchKernelGGL(fir44_down2_kernel<false>, grid, dim3(256), 0, s, x, taps, y, in_h, in_w, out_h, out_w, pad_x0, pad_y0, flip_taps);
-        return gc::check_launch("gc_upfirdn2d_f32(fir44_down2)");
+    case FIR_K12: {
+        using Kernel = decltype(&firK_tile_kernel<12, 1, 1>);
+        static constexpr Kernel kernels[3] = {firK_tile_kernel<12, 2, 1>, firK_tile_kernel<12, 1, 2>, firK_tile_kernel<12, 1, 1>};
+        launch(kernels[up_x == 2 ? 0 : down_x == 2 ? 1 : 2], in_h, in_w, out_h, out_w, pad_x0, pad_y0, flip_taps);
+        break;
     }
-    if (square44 && up_x == 2 && down_x == 1) {
-        dim3 grid(gc::ceil_div(out_w, U_TW), gc::ceil_div(out_h, U_TH), planes);
-        const int ey = pad_y0 & 1, ex = pad_x0 & 1;     // parity of (tile origin - pad); tile origins are multiples of 4
-#define GC_UP2(EY, EX)                                                                                                             \
-        if (ey == EY && ex == EX) {                                                                                                \
-            if (vec_ok) hipLaunchKernelGGL((fir44_up2_kernel<EY, EX, true>), grid, dim3(256), 0, s, x, taps, y, in_h, in_w, out_h, out_w, pad_x0, pad_y0, flip_taps); \
-            else hipLaunchKernelGGL((fir44_up2_kernel<EY, EX, false>), grid, dim3(256), 0, s, x, taps, y, in_h, in_w, out_h, out_w, pad_x0, pad_y0, flip_taps);       \
-        }
-        GC_UP2(0, 0) GC_UP2(0, 1) GC_UP2(1, 0) GC_UP2(1, 1)
-#undef GC_UP2
-        return gc::check_launch("gc_upfirdn2d_f32(fir44_up2)");
+    default:
+        launch(generic_kernel, planes, in_h, in_w, out_h, out_w, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_y0, flip_taps);
     }
-    // 12 x 12 taps (sym6 x sym6) with (up, down) in {(2, 1), (1, 2), (1, 1)} on planes worth tiling: the ADA anti-aliasing passes
-    if (kh == 12 && kw == 12 && up_x == up_y && down_x == down_y && up_x * down_x <= 2 && planes <= 65535 && out_w >= 32 && out_h >= 8)
-        return launch_firK<12>(x, taps, y, planes, in_h, in_w, out_h, out_w, up_x, down_x, pad_x0, pad_y0, flip_taps, s);
-    if (kh * kw > MAX_GENERIC_TAPS) return gc::fail(GC_ERR_UNSUPPORTED, "gc_upfirdn2d_f32: %d x %d taps exceed %d", kh, kw, MAX_GENERIC_TAPS);
-    const size_t total = (size_t)planes * out_h * out_w;
-    const int blocks = (int)std::min<size_t>((total + 255) / 256, 256 * 16);
-    hipLaunchKernelGGL(generic_kernel, dim3(blocks), dim3(256), 0, s, x, taps, y, planes, in_h, in_w, out_h, out_w, kh, kw,
-                       up_x, up_y, down_x, down_y, pad_x0, pad_y0, flip_taps);
-    return gc::check_launch("gc_upfirdn2d_f32(generic)");
+    return gc::check_launch(p.name);
 }
 
 }  // namespace
+
+extern "C" int gc_upfirdn2d_variant_name(int planes, int out_h, int out_w, int kh, int kw, int up, int down, char* name, int name_bytes) {
+    if (!name || name_bytes < 128) return gc::fail(GC_ERR_BAD_ARG, "gc_upfirdn2d_variant_name: null pointer or fewer than 128 bytes");
+    const FirPlan p = plan_fir(kh, kw, up, up, down, down, planes, out_h, out_w);
+    snprintf(name, name_bytes, "%s", p.name);
+    return p.rc;
+}
 
 extern "C" int gc_upfirdn2d_f32(const float* x, const float* taps, float* y,
                                 int planes, int in_h, int in_w, int out_h, int out_w,
@@ -688,7 +683,8 @@ extern "C" int gc_upfirdn2d_pitched_f32(const float* x, const float* taps, float
 
 extern "C" int gc_upfirdn2d_actbwd_tiles(int out_h, int out_w) {
     if (out_h <= 0 || out_w <= 0) return 0;
-    return gc::ceil_div(out_w, TW) * gc::ceil_div(gc::ceil_div(out_h, TH), GC_FIR_NT);
+    const dim3 g = tiles(out_h, out_w, TH, TW, 1);          // the grid plan_fir gives the tile kernel, for one plane
+    return g.x * g.y;
 }
 
 extern "C" int gc_upfirdn2d_actbwd_f32(const float* gy, const float* y_ref, const float* noise, const float* taps, float* gx, float* psum, float* pdot,

@@ -135,6 +135,8 @@ class HipBackend:
     _MODES = _lib.MODE_IDS
     _conv_plans = {}      # (shape, geometry, mode) -> the library's per-shape answers (see conv2d)
     _chunks = {}          # plane size -> gc_bias_act_bwd_chunks
+    _fir_kernels = {}     # (taps, up, down, output, planes) -> gc_upfirdn2d_variant_name
+    _FIR_TILE = 'fir44_tile_kernel'      # what the fused FIR entries run and are timed under: upfirdn2d_act_supported is "the plan names this kernel"
 
     def _bwd_chunks(self, inner):
         v = self._chunks.get(inner)
@@ -193,27 +195,25 @@ class HipBackend:
             return y
         self._launch(dev, 'gc_upfirdn2d_f32', _lib.ptr(x), _lib.ptr(taps), _lib.ptr(y), n * c, h, w, out_h, out_w,
                      taps.shape[0], taps.shape[1], up, up, down, down, pad_x0, pad_y0, int(flip), _lib.stream_of(x),
-                     timed=self.timer and (lambda: ('fir44', self._fir_kernel_name(taps, up, down, out_h, out_w, n * c), 4.0 * (x.numel() + y.numel()))))
+                     timed=self.timer and (lambda: ('fir44', self._fir_kernel(taps, up, down, out_h, out_w, n * c), 4.0 * (x.numel() + y.numel()))))
         return y
+
+    @staticmethod
+    def _fir_kernel(taps, up, down, out_h, out_w, planes):
+        """The kernel gc_upfirdn2d_f32 runs for these extents, from the launcher's own plan (gc_upfirdn2d_variant_name: no launch), asked once
+        per shape; '' for a shape the library refuses (the launch then says why)."""
+        key = (taps.shape, up, down, out_h, out_w, planes)
+        name = HipBackend._fir_kernels.get(key)
+        if name is None:
+            buf = ctypes.create_string_buffer(128)
+            rc = _lib.load().gc_upfirdn2d_variant_name(planes, out_h, out_w, taps.shape[0], taps.shape[1], up, down, buf, 128)
+            name = HipBackend._fir_kernels[key] = buf.value.decode() if rc == 0 else ''
+        return name
 
     @staticmethod
     def upfirdn2d_act_supported(taps, up, down, out_h, out_w, planes):
         """Shapes gc_upfirdn2d_act_f32 takes (the 4x4 tile kernel); everything else runs FIR and activation as two launches."""
-        return tuple(taps.shape) == (4, 4) and up == 1 and down == 1 and out_w >= 64 and out_h >= 16 and planes <= 65535
-
-    @staticmethod
-    def _fir_kernel_name(taps, up, down, out_h, out_w, planes):
-        """The kernel gc_upfirdn2d_f32 runs for these extents (what the timer files the launch under): mirrors its dispatch."""
-        if tuple(taps.shape) == (4, 4) and planes <= 65535:
-            if up == 1 and down == 1 and out_w >= 64 and out_h >= 16:
-                return 'fir44_tile_kernel'
-            if up == 1 and down == 1 and (out_h + 3) * (out_w + 3) <= 1296:
-                return 'fir44_small_kernel'
-            if (up, down) == (1, 2) and out_w >= 32 and out_h >= 8:
-                return 'fir44_down2_kernel'
-            if (up, down) == (2, 1) and out_w >= 32 and out_h >= 8:
-                return 'fir44_up2_kernel'
-        return 'upfirdn2d_generic_kernel'
+        return HipBackend._fir_kernel(taps, up, down, out_h, out_w, planes) == HipBackend._FIR_TILE
 
     def upfirdn2d_act(self, x, taps, pad_x0, pad_y0, out_h, out_w, flip, bias, noise, noise_w, slope, gain, activate=True, out_pitch=0):
         """gain * lrelu(FIR(x) + noise_w * noise + bias); see gc_upfirdn2d_act_f32 (gc_upfirdn2d_pitched_f32 for a row-pitched x)."""
@@ -223,7 +223,7 @@ class HipBackend:
         y = self._empty_rows(n, c, out_h, out_w, out_pitch, dev)
         if y.numel() == 0:
             return y
-        timed = self.timer and (lambda: ('fir44', 'fir44_tile_kernel', 4.0 * (x.numel() + y.numel())))
+        timed = self.timer and (lambda: ('fir44', self._FIR_TILE, 4.0 * (x.numel() + y.numel())))
         if pitch or out_pitch or not activate:
             self._launch(dev, 'gc_upfirdn2d_pitched_f32', _lib.ptr(x), _lib.ptr(taps), _lib.ptr(y), n, c, h, w, pitch or w, out_h, out_w, out_pitch or out_w,
                          taps.shape[0], taps.shape[1], pad_x0, pad_y0, int(flip), int(bool(activate)), _lib.ptr(bias), _lib.ptr(noise), _lib.ptr(noise_w),
@@ -247,7 +247,7 @@ class HipBackend:
             return y
         self._launch(dev, 'gc_upfirdn2d_mask_f32', _lib.ptr(x), _lib.ptr(taps), _lib.ptr(y), n, c, h, w, pitch or w, out_h, out_w, taps.shape[0], taps.shape[1],
                      pad_x0, pad_y0, int(flip), _lib.ptr(mask_ref), float(slope), float(gain), _lib.stream_of(x),
-                     timed=self.timer and (lambda: ('fir44', 'fir44_tile_kernel', 4.0 * (x.numel() + 2 * y.numel()))))
+                     timed=self.timer and (lambda: ('fir44', self._FIR_TILE, 4.0 * (x.numel() + 2 * y.numel()))))
         return y
 
     def upfirdn2d_actbwd(self, gy, y_ref, noise, taps, pad_x0, pad_y0, out_h, out_w, flip, slope, gain):
@@ -263,7 +263,7 @@ class HipBackend:
         self._launch(dev, 'gc_upfirdn2d_actbwd_f32', _lib.ptr(gy), _lib.ptr(y_ref), _lib.ptr(noise), _lib.ptr(taps), _lib.ptr(gx), _lib.ptr(psum), _lib.ptr(pdot),
                      n, c, h, w, out_h, out_w, out_pitch, taps.shape[0], taps.shape[1], pad_x0, pad_y0, int(flip),
                      float(slope), float(gain), _lib.stream_of(gy),
-                     timed=self.timer and (lambda: ('fir44', 'fir44_tile_kernel', 4.0 * (2 * gy.numel() + gx.numel()))))
+                     timed=self.timer and (lambda: ('fir44', self._FIR_TILE, 4.0 * (2 * gy.numel() + gx.numel()))))
         return gx, psum, pdot
 
     # -- backward of a fused (<= 3 -> n) 1x1 convolution + bias + leaky-ReLU (D's FromRGB layer) without an activation-backward pass -------

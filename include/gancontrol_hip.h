@@ -70,6 +70,12 @@ int gc_upfirdn2d_f32(const float* x, const float* taps, float* y,
                      int kh, int kw, int up_x, int up_y, int down_x, int down_y,
                      int pad_x0, int pad_y0, int flip_taps, gc_stream_t stream);
 
+/* The kernel gc_upfirdn2d_f32 runs for this shape (up_x = up_y = up, down_x = down_y = down), from the launcher's own plan; no launch, no
+ * GPU needed.  name (>= 128 bytes) receives one of fir44_tile_kernel, fir44_small_kernel, fir44_down2_kernel, fir44_up2_kernel,
+ * firK_tile_kernel<12>, upfirdn2d_generic_kernel.  The fused and pitched entries below take exactly the shapes named fir44_tile_kernel.
+ * GC_ERR_UNSUPPORTED for a shape no kernel takes (more than 1024 taps), GC_ERR_BAD_ARG for a non-positive extent or factor. */
+int gc_upfirdn2d_variant_name(int planes, int out_h, int out_w, int kh, int kw, int up, int down, char* name, int name_bytes);
+
 /* K1 with the NoiseInjection + FusedLeakyReLU that follow the Blur of an up-sampling StyledConv
  * (gan_model.py:295-307 then :402-408) applied before the result is stored:
  *

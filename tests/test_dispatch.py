@@ -292,6 +292,57 @@ def test_unmasked_stride2_kernel_takes_only_outputs_that_read_inside_the_plane(o
     assert conv_variant(geom, 64, 20, 32, 'bf16x3', (67, 67)).startswith(prefix)
 
 
+# ---- upfirdn2d (gc_upfirdn2d_variant_name: the plan the FIR launcher follows; HipBackend routes and times by the same answer) ----
+
+def _fir_probe(planes, out_h, out_w, k, up, down):
+    import ctypes
+    buf = ctypes.create_string_buffer(128)
+    rc = _lib.load().gc_upfirdn2d_variant_name(planes, out_h, out_w, k, k, up, down, buf, 128)
+    return buf.value.decode() if rc == 0 else rc
+
+
+# (planes, out_h, out_w, taps, up, down) -> kernel, FFHQ-1024 step at B = 4
+STEP_FIR_SHAPES = [
+    # the Blur behind a transposed convolution of G (and its adjoint): the tile kernel from 64 x 64 up, whole planes in LDS below
+    ((4 * 32, 1024, 1024, 4, 1, 1), 'fir44_tile_kernel'),
+    ((4 * 64, 512, 512, 4, 1, 1), 'fir44_tile_kernel'),
+    ((4 * 512, 64, 64, 4, 1, 1), 'fir44_tile_kernel'),
+    ((4 * 512, 32, 32, 4, 1, 1), 'fir44_small_kernel'),
+    ((4 * 512, 8, 8, 4, 1, 1), 'fir44_small_kernel'),
+    # the Blur in front of a stride-2 convolution of D, (H + 1) wide, and its adjoint, (H + 3) wide
+    ((4 * 32, 1025, 1025, 4, 1, 1), 'fir44_tile_kernel'),
+    ((4 * 512, 65, 65, 4, 1, 1), 'fir44_tile_kernel'),
+    ((4 * 512, 33, 33, 4, 1, 1), 'fir44_small_kernel'),
+    ((4 * 512, 35, 35, 4, 1, 1), 'upfirdn2d_generic_kernel'),      # the adjoint at 32 x 32: too large for LDS, too low for a tile
+    ((4 * 512, 5, 5, 4, 1, 1), 'fir44_small_kernel'),
+    # Upsample of the RGB skip (3 channels) and its adjoint
+    ((4 * 3, 1024, 1024, 4, 2, 1), 'fir44_up2_kernel'),
+    ((4 * 3, 32, 32, 4, 2, 1), 'fir44_up2_kernel'),
+    ((4 * 3, 16, 16, 4, 2, 1), 'upfirdn2d_generic_kernel'),
+    ((4 * 3, 512, 512, 4, 1, 2), 'fir44_down2_kernel'),
+    # the decimating FIR of D's ResBlock skip path and its adjoint
+    ((4 * 32, 512, 512, 4, 1, 2), 'fir44_down2_kernel'),
+    ((4 * 512, 32, 32, 4, 1, 2), 'fir44_down2_kernel'),
+    ((4 * 512, 16, 16, 4, 1, 2), 'upfirdn2d_generic_kernel'),
+    ((4 * 32, 1024, 1024, 4, 2, 1), 'fir44_up2_kernel'),
+    # ADA: 12 x 12 sym6 taps, 1036 -> 2061 up, 2061 -> 1025 down, and the adjoint of the first
+    ((4 * 3, 2061, 2061, 12, 2, 1), 'firK_tile_kernel<12>'),
+    ((4 * 3, 1025, 1025, 12, 1, 2), 'firK_tile_kernel<12>'),
+    ((4 * 3, 1036, 1036, 12, 1, 2), 'firK_tile_kernel<12>'),
+]
+
+
+@pytest.mark.parametrize('shape,kernel', STEP_FIR_SHAPES)
+def test_step_fir_shapes_reach_their_kernels(shape, kernel):
+    assert _fir_probe(*shape) == kernel, shape
+
+
+def test_fir_probe_refuses_what_no_kernel_takes():
+    assert _fir_probe(1, 16, 64, 33, 1, 1) == -2          # 1089 taps: more than the generic kernel's 1024
+    assert _fir_probe(1, 16, 64, 32, 1, 1) == 'upfirdn2d_generic_kernel'
+    assert _fir_probe(1, 0, 64, 4, 1, 1) == -1 and _fir_probe(-1, 16, 64, 4, 1, 1) == -1 and _fir_probe(1, 16, 64, 4, 0, 1) == -1
+
+
 # ---- the whole decision table (tools/dispatch_table.py): every probe and every size / pitch query over a fixed descriptor grid, frozen as a digest ----
 
 def test_dispatch_table_matches_the_frozen_digest():

@@ -113,6 +113,55 @@ def test_upfirdn2d_small_plane_kernel(shape):
         assert rel_err(a[..., :shape[3] - 2], b[..., :shape[3] - 2]) < 1e-6
 
 
+def _fir_probe(planes, out_h, out_w, k, up, down):
+    import ctypes
+    from gan_control_amd import _lib
+    buf = ctypes.create_string_buffer(128)
+    assert _lib.load().gc_upfirdn2d_variant_name(planes, out_h, out_w, k, k, up, down, buf, 128) == 0
+    return buf.value.decode()
+
+
+# (taps, up, down, out_h, out_w, kernel): both sides of every extent threshold of the FIR plan (plan_fir, upfirdn2d.hip)
+FIR_BOUNDARY_CASES = [
+    (4, 1, 1, 16, 64, 'fir44_tile_kernel'), (4, 1, 1, 15, 64, 'fir44_small_kernel'), (4, 1, 1, 16, 63, 'fir44_small_kernel'),
+    (4, 1, 1, 15, 200, 'upfirdn2d_generic_kernel'), (4, 1, 1, 100, 63, 'upfirdn2d_generic_kernel'),
+    (4, 1, 1, 33, 33, 'fir44_small_kernel'), (4, 1, 1, 34, 33, 'upfirdn2d_generic_kernel'),
+    (4, 1, 2, 8, 32, 'fir44_down2_kernel'), (4, 1, 2, 7, 32, 'upfirdn2d_generic_kernel'), (4, 1, 2, 8, 31, 'upfirdn2d_generic_kernel'),
+    (4, 2, 1, 8, 32, 'fir44_up2_kernel'), (4, 2, 1, 7, 32, 'upfirdn2d_generic_kernel'), (4, 2, 1, 8, 31, 'upfirdn2d_generic_kernel'),
+    (12, 2, 1, 8, 32, 'firK_tile_kernel<12>'), (12, 2, 1, 7, 32, 'upfirdn2d_generic_kernel'),
+    (12, 1, 2, 8, 32, 'firK_tile_kernel<12>'), (12, 1, 2, 7, 32, 'upfirdn2d_generic_kernel'),
+]
+
+
+def test_upfirdn2d_plan_boundaries():
+    """Each side of each threshold of the FIR plan: the probe names the kernel, and that kernel computes the FIR (fp64 emulation, both tap orders).
+    Inputs are [2, 3, ., .]; 4 x 4 taps with up = down = 1 run with pad (2, 1), so the input is as large as the output; the resampling cases read
+    out * down / up input samples with pad0 = taps / 2 (the output extent is the caller's: what lies beyond the input reads zeros)."""
+    hip, emu = _be()
+    gen = torch.Generator().manual_seed(7)
+    for ksz, up, down, oh, ow, kernel in FIR_BOUNDARY_CASES:
+        assert _fir_probe(6, oh, ow, ksz, up, down) == kernel, (ksz, up, down, oh, ow)
+        x = torch.randn(2, 3, (oh * down + up - 1) // up, (ow * down + up - 1) // up, generator=gen)
+        k = torch.randn(ksz, ksz, generator=gen)
+        p0 = ksz // 2
+        for flip in (True, False):
+            ref = emu.upfirdn2d(x.double(), k.double(), up, down, p0, p0, oh, ow, flip)
+            out = hip.upfirdn2d(x.to(DEV), k.to(DEV), up, down, p0, p0, oh, ow, flip)
+            assert out.shape == ref.shape
+            assert rel_err(out, ref) < 2e-6, (ksz, up, down, oh, ow, flip)
+    # 65536 planes: one more than gridDim.z holds, so the tile kernel's smallest plane (19 x 67 -> 16 x 64, which also fits LDS whole) goes to the
+    # small-plane kernel, and the fused entries are not offered; the first and the last 8 planes against fp64
+    k = torch.randn(4, 4, generator=gen)
+    assert _fir_probe(65536, 16, 64, 4, 1, 1) == 'fir44_small_kernel' and _fir_probe(65535, 16, 64, 4, 1, 1) == 'fir44_tile_kernel'
+    assert not hip.upfirdn2d_act_supported(k, 1, 1, 16, 64, 65536) and hip.upfirdn2d_act_supported(k, 1, 1, 16, 64, 65535)
+    x = torch.randn(256, 256, 19, 67, device=DEV, generator=torch.Generator(device=DEV).manual_seed(8))
+    ends = torch.cat([x.view(-1, 19, 67)[:8], x.view(-1, 19, 67)[-8:]]).cpu().double().unsqueeze(0)
+    for flip in (True, False):
+        ref = emu.upfirdn2d(ends, k.double(), 1, 1, 0, 0, 16, 64, flip)
+        out = hip.upfirdn2d(x, k.to(DEV), 1, 1, 0, 0, 16, 64, flip).view(-1, 16, 64)
+        assert rel_err(torch.cat([out[:8], out[-8:]]).unsqueeze(0), ref) < 2e-6, flip
+
+
 @pytest.mark.parametrize('up,down', [(1, 2), (2, 1)])
 @pytest.mark.parametrize('shape', [(2, 3, 64, 130), (1, 2, 257, 255), (1, 1, 33, 513), (3, 1, 128, 128), (1, 2, 16, 140)])
 def test_upfirdn2d_resampling_tile_kernels(up, down, shape):

@@ -1,6 +1,7 @@
-"""The decision table of the convolution dispatch: every kernel-variant probe and every size / pitch query of the library over a fixed descriptor grid.
+"""The decision table of the convolution and FIR dispatch: every kernel-variant probe and every size / pitch query of the library over a fixed descriptor grid.
 
-No GPU is needed: gc_conv2d_variant_name and gc_conv2d_wgrad_variant_name run the launchers in their no-launch probe mode, the queries are host code.
+No GPU is needed: gc_conv2d_variant_name and gc_conv2d_wgrad_variant_name run the launchers in their no-launch probe mode, gc_upfirdn2d_variant_name reads the
+plan the FIR launcher follows, the queries are host code.
 tests/golden/dispatch_table.json holds a DIGEST of the table -- per (geometry, column) group the row count, a sha256 over the rows and, for the probe
 columns, the histogram of kernel names -- and tests/test_dispatch.py recomputes it from the built library.  When a digest moves, diff the rows of two builds:
 
@@ -104,8 +105,35 @@ def columns(lib):
     return cols
 
 
+# ---- upfirdn2d (gc_upfirdn2d_variant_name): one column, the kernel plan_fir names ----
+FIR_TAPS = [4, 12, 3, 5]                                    # 3 and 5: nothing but the generic kernel
+FIR_UP_DOWN = [(1, 1), (1, 2), (2, 1), (2, 2), (3, 2)]
+FIR_PLANES = [1, 65535, 65536]                              # gridDim.z holds 65535
+# both sides of every extent threshold: 16 x 64 (tile kernel), 8 x 32 (down2 / up2 / 12-tap tile kernels), and (out_h + 3) * (out_w + 3) <= 1296 (small-plane kernel:
+# 36 * 36 = 18 * 72 = 12 * 108 = 1296; 36 * 37 = 1332)
+FIR_OUT = [(h, w) for h in (7, 8, 15, 16, 33, 34) for w in (31, 32, 63, 64)] + [(33, 33), (33, 34), (34, 33), (15, 69), (15, 70), (69, 15), (70, 15), (9, 105), (9, 106),
+                                                                                (15, 200), (100, 63), (1024, 1024), (1025, 1025)]
+
+
+def fir_grid():
+    """(planes, out_h, out_w, taps, up, down) of every FIR row; the last row has more taps than any kernel takes."""
+    from test_dispatch import STEP_FIR_SHAPES
+    shapes = [(planes, oh, ow, k, up, down) for k in FIR_TAPS for up, down in FIR_UP_DOWN for planes in FIR_PLANES for oh, ow in FIR_OUT]
+    shapes += [shape for shape, _ in STEP_FIR_SHAPES]
+    shapes.append((1, 16, 64, 33, 1, 1))
+    return list(dict.fromkeys(shapes))
+
+
+def fir_rows(lib):
+    buf = ctypes.create_string_buffer(128)
+    for t in fir_grid():
+        planes, oh, ow, k, up, down = t
+        rc = lib.gc_upfirdn2d_variant_name(planes, oh, ow, k, k, up, down, buf, 128)
+        yield 'fir:%d,%d,%d|fir_variant[name]' % t[3:], ','.join(map(str, t)) + ' -> ' + (buf.value.decode() if rc == 0 else 'rc%d' % rc)
+
+
 def rows():
-    """Yield (group, row text): group = '<taps>,<up>,<down>,<pad>|<column>', row = '<descriptor fields> -> <cell>'."""
+    """Yield (group, row text): group = '<taps>,<up>,<down>,<pad>|<column>', row = '<descriptor fields> -> <cell>'; the FIR groups ('fir:<taps>,<up>,<down>|...') follow."""
     lib = _lib.load()
     cols = columns(lib)
     for t in grid():
@@ -115,6 +143,7 @@ def rows():
         for name, (fn, transposed_too) in cols.items():
             if t[9] == 1 or transposed_too:
                 yield geom + '|' + name, key + ' -> ' + fn(d)
+    yield from fir_rows(lib)
 
 
 def digest():
