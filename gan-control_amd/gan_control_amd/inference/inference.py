@@ -4,6 +4,10 @@ A model directory holds ``args.json`` (``model_config`` / ``training_config``) a
 ``trainers.utils.save_args`` and the trainers' checkpoints write that layout.  Differences from the reference ("Inference API"):
 ``device=None`` picks CUDA when there is one, else the CPU; there is no DataParallel wrapper, ``.model`` is the Generator; z -> w is ONE
 ``fc_stacks_forward`` call (models/op/fc_stack.py) and the generator then runs on ``[latent_w]`` with ``input_is_latent=True``.
+
+The group matrices and interpolation films of the reference's second ``Inference`` class (evaluation/inference_class.py:115-212) are methods
+of this one: ``generate_matrix_by_group``, ``interpolate_by_group``, ``slerp``, ``gen_grid_image_from_latent``, ``make_interpolation_gif``,
+``create_gif``; the blends of a film run on the kernels of models/op/interp.py.
 """
 import json
 import os
@@ -157,6 +161,121 @@ class Inference:
                 size = (int(resize[1]), int(resize[0]))
             image = image.resize(size, Image.BILINEAR)
         return image
+
+    # -- group matrices and interpolation films (reference: evaluation/inference_class.py:115-212) ----------------------------------------
+    @staticmethod
+    def slerp(val, low, high):
+        """Spherical interpolation of the rows of ``low`` and ``high`` at ``val`` in [0, 1], the reference's formula (nothing is clamped)."""
+        low_norm = low / torch.norm(low, dim=1, keepdim=True)
+        high_norm = high / torch.norm(high, dim=1, keepdim=True)
+        omega = torch.acos((low_norm * high_norm).sum(1))
+        so = torch.sin(omega)
+        return (torch.sin((1.0 - val) * omega) / so).unsqueeze(1) * low + (torch.sin(val * omega) / so).unsqueeze(1) * high
+
+    def gen_grid_image_from_latent(self, latent, noise=None, nrow=4, downsample=None):
+        """The PIL grid of ``self.model([latent], noise=noise)`` (a z latent), ``nrow`` images per row."""
+        from ..evaluation.image_grid import grid_image
+        with torch.no_grad():
+            sample, _ = self.model([latent.to(self.device)], noise=noise)
+        return grid_image(sample, nrow=nrow, downsample=downsample)
+
+    def generate_matrix_by_group(self, group, save_path=None, downsample=None, generator=None):
+        """The 6 x 6 matrix in which image (row, col) carries ``group``'s slice of sample ``row`` and the rest of sample ``col``, one shared
+        noise; saved to ``'%s.jpg' % save_path`` when a path is given.  -> the PIL image."""
+        from ..evaluation.generation import gen_matrix
+        self.check_valid_group(group)
+        same_chunk = self.batch_utils.place_in_latent_dict[group]
+        image = gen_matrix(self.model, same_noise_per_id=False, same_chunk=same_chunk, same_noise_for_all=True, downsample=downsample,
+                           generator=generator)
+        if save_path is not None:
+            image.save('%s.jpg' % save_path)
+        return image
+
+    def interpolation_latents(self, group, latent_1, latent_from, latent_to, pics_per_interpolation=10, interpolation='slerp'):
+        """The z of every frame of one segment, both films: [2, P, B, L] (models/op/interp.py).  [0]: ``group``'s slice stays ``latent_1``'s
+        and the rest moves from ``latent_from`` to ``latent_to``; [1]: only ``group``'s slice moves, the rest stays ``latent_1``'s."""
+        from ..models.op.interp import interpolate_latents, interpolation_weights
+        self.check_valid_group(group)
+        lo, hi = self.batch_utils.place_in_latent_dict[group]
+        wa, wb = interpolation_weights(pics_per_interpolation, interpolation)
+        return interpolate_latents(latent_1, latent_from, latent_to, lo, hi, wa, wb, interpolation)
+
+    @torch.no_grad()
+    def interpolate_by_group(self, group, save_path, batch=4, num_of_intermediate_latents=4, pics_per_interpolation=10, interpolation='slerp',
+                             same_noise=True, downsample=None, idx=None, generator=None, return_list=False):
+        """Two films of ``num_of_intermediate_latents`` segments of ``pics_per_interpolation`` frames each, ``batch`` walks side by side in a
+        frame: in the first ``group`` is frozen at ``latent_1``'s and everything else moves, in the second only ``group`` moves.  Frames go to
+        ``<save_path>/freeze_group/%06d.jpg`` and ``<save_path>/freeze_not_same_group/%06d.jpg``, the GIFs to
+        ``<save_path>/freeze_group_<basename>[%04d idx].gif`` and ``<save_path>/freeze_not_group_<basename>[%04d idx].gif``.  -> the two lists
+        of PIL images; with ``return_list=True`` nothing is written and the two float tensors [frames, batch, 3, h, w] of generator outputs
+        come back on the host.  ``generator``: a ``torch.Generator`` that makes the call repeatable.
+
+        Per segment ONE interpolate_latents call and ONE ``self.style`` call over the 2 P B rows; per frame ONE blend_noise call into a
+        reused list (with ``same_noise`` it blends the noise with itself, as the reference does: that is not the noise bit for bit), two
+        generator calls on w and two grid images."""
+        from ..evaluation.generation import _make_noise, _randn
+        from ..evaluation.image_grid import grid_image
+        from ..models.op.interp import blend_noise, interpolation_weights
+        self.check_valid_group(group)
+        dtype, size = self._dtype(), self.config.model_config['latent_size']
+        pics = int(pics_per_interpolation)
+        noise = [n.to(dtype).expand(batch, -1, -1, -1).clone() for n in _make_noise(self.model, self.device, generator)]
+        latent_1 = _randn((1, size), self.device, generator).to(dtype).expand(batch, -1)
+        latent_2 = [_randn((batch, size), self.device, generator).to(dtype) for _ in range(num_of_intermediate_latents)]
+        if same_noise:
+            noise_2 = [noise for _ in range(num_of_intermediate_latents)]
+        else:
+            noise_2 = [[n.to(dtype) for n in _make_noise(self.model, self.device, generator, batch_size=batch)] for _ in range(num_of_intermediate_latents)]
+        na, nb = interpolation_weights(pics, 'linear')          # the noise is blended linearly whatever the latents' rule
+        z1, noise1, frame_noise = latent_1, noise, None
+        films = ([], [])
+        for z2, noise2 in zip(latent_2, noise_2):
+            z = self.interpolation_latents(group, latent_1, z1, z2, pics, interpolation)
+            w = self.style(z.reshape(2 * pics * batch, size)).reshape(2, pics, batch, -1)
+            for f in range(pics):
+                frame_noise = blend_noise(noise1, noise2, na[f], nb[f], out=frame_noise)
+                for film in (0, 1):
+                    sample, _ = self.model([w[film, f]], input_is_latent=True, noise=frame_noise)
+                    films[film].append(sample.cpu() if return_list else grid_image(sample, nrow=batch, downsample=downsample))
+            z1, noise1 = z2, noise2
+        if return_list:
+            return torch.stack(films[0], 0), torch.stack(films[1], 0)
+        tail = os.path.split(save_path)[-1] + ('' if idx is None else '%04d' % idx)
+        for images, folder, name in ((films[0], 'freeze_group', '../freeze_group_' + tail),
+                                     (films[1], 'freeze_not_same_group', '../freeze_not_group_' + tail)):
+            os.makedirs(os.path.join(save_path, folder), exist_ok=True)
+            self.make_interpolation_gif(images, os.path.join(save_path, folder), name=name)
+        return films
+
+    def make_interpolation_gif(self, image_list, save_path, name='sample'):
+        """``image_list`` as ``save_path``/%06d.jpg and as the GIF ``save_path``/``name``.gif."""
+        for i, image in enumerate(image_list):
+            image.save(os.path.join(save_path, '%06d.jpg' % i))
+        self.create_gif(save_path, name=name)
+
+    @staticmethod
+    def create_gif(save_dir, delay=50, name='sample'):
+        """The reference's ``convert -delay 50 -loop 0 -resize 1024x256 *.jpg <name>.gif`` with PIL, no subprocess: every .jpg of ``save_dir``
+        in sorted order, scaled to fit inside 1024 x 256 with its aspect ratio kept, ``delay`` hundredths of a second per frame, looping
+        forever.  Image.save(save_all=True) folds a frame that repeats its predecessor into it (the last frame of a segment is the first of
+        the next), so the frames are encoded one by one, as ``convert`` writes them."""
+        from PIL import GifImagePlugin, Image
+        frames = []
+        for fname in sorted(n for n in os.listdir(save_dir) if n.endswith('.jpg')):
+            with Image.open(os.path.join(save_dir, fname)) as im:
+                im = im.convert('RGB')
+            scale = min(1024 / im.size[0], 256 / im.size[1])
+            size = (min(1024, max(1, round(im.size[0] * scale))), min(256, max(1, round(im.size[1] * scale))))
+            frames.append((im if size == im.size else im.resize(size, Image.BILINEAR)).convert('P', palette=Image.ADAPTIVE))
+        if not frames:
+            raise FileNotFoundError('no .jpg frames under %s' % save_dir)
+        with open(os.path.normpath(os.path.join(save_dir, name + '.gif')), 'wb') as fp:
+            for block in GifImagePlugin.getheader(frames[0], info={'loop': 0, 'duration': 10 * delay})[0]:
+                fp.write(block)
+            for frame in frames:
+                for block in GifImagePlugin.getdata(frame, duration=10 * delay, include_color_table=True):
+                    fp.write(block)
+            fp.write(b';')
 
     @staticmethod
     def retrieve_model(model_dir, device=None):

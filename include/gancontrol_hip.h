@@ -735,6 +735,40 @@ int gc_pairwise_f32(const float* s, int64_t s_stride, const float* q, int64_t q_
                     const int32_t* s_pid, const int32_t* q_pid, float* best, int32_t* best_idx, void* workspace, size_t workspace_bytes,
                     gc_stream_t stream);
 
+/* ---- group interpolation of the inference API (models/op/interp.py, csrc/interp.hip) --------------------------------------------------------
+ * The blends of Inference.interpolate_by_group (reference: evaluation/inference_class.py:125-185), each in one launch.
+ *
+ * gc_latent_interp_f32: every frame of one interpolation segment, both films.  fixed, from, to: DEVICE [batch, latent] float32, elements of
+ * a row adjacent, row b at p + b * stride (strides in ELEMENTS: at least latent, or 0 -- the inputs are only read and the reference's latent_1
+ * is one expanded row; any 4-byte alignment).  0 <= lo < hi <= latent names the group G = [lo, hi); S = [0, lo), E = [hi, latent).  wa, wb: HOST
+ * arrays of `frames` floats (1 .. 64), carried in the kernel arguments.  out: DEVICE dense [2, frames, batch, latent]:
+ *   out[0, f, b] = [ blend_f(from, to) on S | fixed on G | blend_f(from, to) on E ]          (the group is frozen)
+ *   out[1, f, b] = [ fixed on S | blend_f(from, to) on G | fixed on E ]                      (only the group moves)
+ *   GC_INTERP_LINEAR, GC_INTERP_SQRT: blend_f(x, y) = fl(fl(wa[f] * x) + fl(wb[f] * y)) -- two rounded products and a rounded sum, never an
+ *     FMA: bit for bit what ATen computes for a * x + b * y with float32 scalars (the two modes differ in the weights the caller passes);
+ *   GC_INTERP_SLERP: per row and per slice (S, G and E each on its own), omega = acos(x.y / (|x| |y|)), ca = sin(wa[f] omega) / sin(omega),
+ *     cb = sin(wb[f] omega) / sin(omega), blend_f(x, y) = fl(fl(ca * x) + fl(cb * y)).  The row sums are taken once per row in float64 in an
+ *     order fixed by the extents (no atomics: the same inputs give the same bits), the coefficients computed in float64 and rounded once.
+ *     Nothing is clamped: parallel slices are as undefined as in the reference.
+ * An empty S (lo == 0) or E (hi == latent) is neither read nor written and forms no coefficient.  Only out is stored; no byte outside the
+ * `latent` columns of the rows is loaded.  Null pointers, extents below 1, a group outside the row, frames < 1, an unknown mode and a stride
+ * that is negative or in (0, latent) return GC_ERR_BAD_ARG, more than 64 frames or 2^31 output elements GC_ERR_UNSUPPORTED; nothing is
+ * launched then.
+ *
+ * gc_noise_blend_f32: out[m][i] = fl(fl(wa * a[m][i]) + fl(wb * b[m][i])) for i < counts[m], over a whole list of maps in ONE launch.
+ * a, b, out: HOST arrays of n (1 .. 32) DEVICE pointers to dense float32; counts: HOST array, counts[m] >= 1.  A map whose three pointers
+ * are 16-byte aligned moves in 16-byte words with a 4-byte tail of counts[m] % 4 elements, any other one in 4-byte words.  a[m] and b[m] may
+ * be the same memory; no output may overlap an input or another output.  Null pointers, n < 1, a count below 1 and an overlap return
+ * GC_ERR_BAD_ARG, more than 32 maps GC_ERR_UNSUPPORTED; nothing is launched then. */
+#define GC_INTERP_LINEAR 0
+#define GC_INTERP_SLERP 1
+#define GC_INTERP_SQRT 2
+int gc_latent_interp_f32(const float* fixed, int64_t fixed_stride, const float* from, int64_t from_stride, const float* to, int64_t to_stride,
+                         int batch, int latent, int lo, int hi, const float* wa, const float* wb, int frames, int mode, float* out,
+                         gc_stream_t stream);
+int gc_noise_blend_f32(const float* const* a, const float* const* b, float* const* out, const int64_t* counts, int n, float wa, float wb,
+                       gc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
