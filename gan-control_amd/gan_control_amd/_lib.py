@@ -140,6 +140,10 @@ SIGNATURES = {
     'gc_noise_normalize_workspace': (_sz, [_vp, _i32]),
     'gc_noise_normalize_f32': (_i32, [_vp, _vp, _i32, _vp, _sz, _vp]),
     'gc_fc_stacks_fwd_f32': (_i32, [_vp] * 12 + [_i32, _i32, _vp]),
+    'gc_fc_stack_fwd_save_f32': (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
+    'gc_rec_loss_grad_f32': (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
+    'gc_fc_stack_bwd_adam_f32': (_i32, [_vp, _i64, _i32, _i32] + [_vp] * 11 + [_i32] + [ctypes.c_double] * 6 + [_vp]),
+    'gc_fc_train_launches': (_i64, []),
     'gc_pairwise_workspace': (_sz, [_i32, _i32, _i32]),
     'gc_pairwise_f32': (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'gc_latent_interp_f32': (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp]),

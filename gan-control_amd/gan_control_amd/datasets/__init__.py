@@ -1,3 +1,3 @@
-from .dataframe_dataset import DataFrameDataSet, get_dataframe_data_loader
+from .dataframe_dataset import DataFrameDataSet, DeviceFrame, get_dataframe_data_loader
 
-__all__ = ['DataFrameDataSet', 'get_dataframe_data_loader']
+__all__ = ['DataFrameDataSet', 'DeviceFrame', 'get_dataframe_data_loader']

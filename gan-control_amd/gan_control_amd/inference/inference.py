@@ -94,8 +94,13 @@ class Inference:
         self.mean_w_latents = {key: self.mean_w_latent[lo:hi] for key, (lo, hi) in self._places().items()}
 
     # -- noise ------------------------------------------------------------------------------------------------------------------------
-    def reset_noise(self):
-        self.noise = [n.to(self._dtype()) for n in self.model.make_noise(device=self.device)]
+    def reset_noise(self, generator=None):
+        """Fresh [1, 1, h, w] noise maps; drawn from ``generator`` (a ``torch.Generator``) when one is given."""
+        if generator is None:
+            self.noise = [n.to(self._dtype()) for n in self.model.make_noise(device=self.device)]
+        else:
+            from ..evaluation.generation import _make_noise
+            self.noise = [n.to(self._dtype()) for n in _make_noise(self.model, self.device, generator)]
 
     @staticmethod
     def expend_noise(noise, batch_size):
@@ -104,15 +109,18 @@ class Inference:
 
     # -- generation -------------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def gen_batch(self, batch_size=1, normalize=True, latent=None, input_is_latent=False, static_noise=True, truncation=1, **kwargs):
+    def gen_batch(self, batch_size=1, normalize=True, latent=None, input_is_latent=False, static_noise=True, truncation=1, generator=None,
+                  **kwargs):
         """-> (images, latent, latents): ``latent`` is the z that was drawn or given -- the w that entered the generator when a w was given
         or truncation applied -- and ``latents`` the [B, n_latent, 512] tensor the generator returns.  kwargs: ``group='random'`` with a
-        given w latent redraws that group's slice.  The caller's tensor is never written."""
+        given w latent redraws that group's slice.  The caller's tensor is never written.  ``generator``: a ``torch.Generator`` the drawn
+        latent and the static noise maps come from, which makes a call repeatable (as in ``interpolate_by_group``)."""
         if truncation < 1 and self.mean_w_latents is None:
             self.calc_mean_w_latents()
         size = self.config.model_config['latent_size']
         if latent is None:
-            latent = torch.randn(batch_size, size, device=self.device, dtype=self._dtype())
+            latent = torch.randn(batch_size, size, device=self.device, dtype=self._dtype()) if generator is None else \
+                torch.randn(batch_size, size, device=generator.device, generator=generator).to(self.device, self._dtype())
         elif input_is_latent:
             latent = latent.to(self.device)
             for group_key, value in kwargs.items():
@@ -126,7 +134,7 @@ class Inference:
             latent = latent.to(self.device)
         injection_noise = None
         if static_noise:
-            self.reset_noise()
+            self.reset_noise(generator)
             injection_noise = self.noise           # [1, 1, h, w] maps: StyledConv broadcasts them over the batch, bit for bit expend_noise
         latent_w = latent if input_is_latent else self.style(latent)
         if truncation < 1:

@@ -710,6 +710,55 @@ int gc_fc_stacks_fwd_f32(const float* const* x, const int64_t* x_stride, float* 
                          const float* const* w, const float* const* bias, const int32_t* out_dim, const float* alpha, const float* beta,
                          int n_stacks, int batch, gc_stream_t stream);
 
+/* ---- one optimisation step of one FC stack: controller training (models/op/fc_train.py, csrc/fc_train.hip) ------------------------------
+ * What ControllerTrainer.controller_update computes for the `latent_rec` objective (controller_trainer.py:202-229) -- forward, L1 / MSE
+ * against a column slice of the w latents, backward, torch.optim.Adam -- in n_layers + 2 launches.  The stack is ONE stack of
+ * gc_fc_stacks_fwd_f32 without PixelNorm, described by the same per-layer HOST arrays (w DEVICE [out_dim, in] dense, bias DEVICE [out_dim]
+ * and required here, out_dim, alpha, beta) and the same input description (x, x_stride in ELEMENTS, in_dim; any 4-byte alignment).
+ * Workspaces: `acts` and `grads` are DEVICE float arrays of batch * sum_l out_dim[l] elements; layer l's part is the dense
+ * [batch, out_dim[l]] block at element offset batch * sum_(i<l) out_dim[i] of either.
+ * Built: 1 .. 8 layers, every width 1 .. 512 (any alignment of the first weight), batch 1 .. 64; anything else returns GC_ERR_UNSUPPORTED;
+ * a null table, pointer or workspace and a row stride shorter than the row GC_ERR_BAD_ARG.  Everything is checked before the first launch.
+ * fp32 FMA only, every sum in an order fixed by the shapes, no atomics, no flags, no grid barrier: the same inputs give the same bits.
+ *
+ * gc_fc_stack_fwd_save_f32: the forward of gc_fc_stacks_fwd_f32 (the same layer code: the same bits), which also stores every layer's
+ * output into its block of acts; the last block is the prediction.  Only acts is stored.
+ *
+ * gc_rec_loss_grad_f32: pred DEVICE dense [batch, n]; target row b at target + b * target_stride (ELEMENTS, at least n: a column slice of
+ * the w latent rows is read in place).  With d = pred - target and N = batch * n:
+ *   GC_REC_LOSS_L1:  *loss = sum |d| / N,   dy = sign(d) / N   (sign(0) = 0)
+ *   GC_REC_LOSS_MSE: *loss = sum d^2 / N,   dy = 2 d / N
+ * dy DEVICE dense [batch, n] (the last block of grads), loss one DEVICE float.  One workgroup.  Only dy and *loss are stored.
+ *
+ * gc_fc_stack_bwd_adam_f32: one launch per layer, last to first.  On entry the last block of grads holds d(loss) / d(prediction) and acts
+ * what gc_fc_stack_fwd_save_f32 stored for the same x and parameters.  Layer l, with dY its block of grads, A_l its block of acts,
+ * A_(l-1) the block before it (x for l = 0) and W [n, k]:
+ *   g = dY * (A_l > 0 ? 1 : 0.2) * sqrt(2)      (the sign of an output is the sign of its pre-activation; an output of 0 takes the 0.2 slope)
+ *   db = beta sum_b g,   dW = alpha g^T A_(l-1),   dX = alpha g W -> the block of grads before it (not computed for l = 0)
+ * and, in the same launch, torch.optim.Adam's update (weight_decay 0, no amsgrad, no maximize) of W, bias and their moments in place:
+ *   m = beta1 m + (1 - beta1) grad,   v = beta2 v + (1 - beta2) grad^2,
+ *   p -= (lr / bias_correction1) * m / (sqrt(v) / bias_correction2_sqrt + eps)
+ * with bias_correction1 = 1 - beta1^t and bias_correction2_sqrt = sqrt(1 - beta2^t) computed by the caller (both > 0, else
+ * GC_ERR_BAD_ARG).  The six scalars arrive in float64; beta, 1 - beta, lr / bias_correction1, bias_correction2_sqrt and eps are each rounded
+ * to float32 once, as torch.optim.Adam hands them to its kernels (1 - beta2 formed from a float32 beta2 is off by up to 4e-6 of its value).
+ * w_m / w_v / b_m / b_v: HOST arrays of n_layers DEVICE pointers to the moments, shaped like w / bias.  A workgroup owns 8 columns of W and
+ * produces dX and dW for them completely, so the gradients of the parameters never reach memory.  Stored: w, bias, the moments and all
+ * blocks of grads but the last.
+ *
+ * gc_fc_train_launches: the number of kernel launches the three entries have issued in this process so far (one each for the forward and the
+ * loss, n_layers for the backward); a refused call adds nothing. */
+#define GC_REC_LOSS_L1 0
+#define GC_REC_LOSS_MSE 1
+int gc_fc_stack_fwd_save_f32(const float* x, int64_t x_stride, int in_dim, int n_layers, const float* const* w, const float* const* bias,
+                             const int32_t* out_dim, const float* alpha, const float* beta, float* acts, int batch, gc_stream_t stream);
+int gc_rec_loss_grad_f32(const float* pred, const float* target, int64_t target_stride, int batch, int n, int kind, float* dy, float* loss,
+                         gc_stream_t stream);
+int gc_fc_stack_bwd_adam_f32(const float* x, int64_t x_stride, int in_dim, int n_layers, float* const* w, float* const* bias,
+                             const int32_t* out_dim, const float* alpha, const float* beta, float* const* w_m, float* const* w_v,
+                             float* const* b_m, float* const* b_v, const float* acts, float* grads, int batch, double lr, double beta1,
+                             double beta2, double eps, double bias_correction1, double bias_correction2_sqrt, gc_stream_t stream);
+int64_t gc_fc_train_launches(void);
+
 /* ---- all-pairs feature distances of the separability evaluation (models/op/pairwise.py, csrc/pairwise.hip) -----------------------------
  * What LossModelClass.calc_distances computes chunk pair by chunk pair (loss_model.py:252-285) and the per-query minimum of
  * calc_same_not_same_list (loss_model.py:214-229), in one call.  s [m, k] (signatures) and q [n, k] (queries): row i at s + i * s_stride,
