@@ -49,6 +49,12 @@ class WsqGroup(ctypes.Structure):
     _fields_ = [('w', _vp), ('g', _vp), ('out', _vp), ('rows', _i32), ('taps', _i32)]
 
 
+class WRefreshItem(ctypes.Structure):
+    """Mirror of ``gc_wrefresh_item`` (its size is compared through gc_weight_refresh_item_bytes: op/weight_refresh.py)."""
+    _fields_ = [('src', _vp), ('ema', _vp), ('w_t', _vp), ('adj', _vp), ('adj2', _vp), ('pack_w', _vp), ('pack_adj', _vp), ('wsq', _vp), ('count', _i64),
+                ('n', _i32), ('k', _i32), ('taps', _i32), ('flip_taps', _i32), ('scale', _f32), ('decay', _f32), ('alpha', _f32)]
+
+
 # the mirrors above in the header's declaration order (gc_struct_sizes)
 STRUCTS = (ConvDesc, ConvEpilogue, WLayoutGroup, WPackGroup, GlinGroup, WsqGroup)
 
@@ -149,6 +155,9 @@ SIGNATURES = {
     'gc_latent_interp_f32': (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp]),
     'gc_noise_blend_f32': (_i32, [_vp, _vp, _vp, _vp, _i32, _f32, _f32, _vp]),
     'gc_weight_layout_f32': (_i32, [_vp, _vp, _i32, _i32, _i32, ctypes.POINTER(_i64 * 3), ctypes.POINTER(_i64 * 3), _i32, _f32, _vp]),
+    'gc_weight_refresh_grouped_f32': (_i32, [ctypes.POINTER(WRefreshItem), _i32, _vp]),
+    'gc_weight_refresh_launches': (_i64, []),
+    'gc_weight_refresh_item_bytes': (_sz, []),
 }
 
 _lib = None

@@ -10,6 +10,7 @@ from .upfirdn2d import upfirdn2d, upfirdn2d_bias_act
 from . import conv2d_gradfix
 from .modulated_conv import modulated_conv2d, modulated_conv2d_act, demod_coefficients
 from .warp import affine_warp_bilinear, reflect_pad
+from . import weight_refresh          # noqa: F401  (installs weight_cache.refresh_runner)
 
 __all__ = ['FusedLeakyReLU', 'fused_leaky_relu', 'fused_noise_bias_act', 'upfirdn2d', 'upfirdn2d_bias_act', 'conv2d_gradfix',
            'modulated_conv2d', 'modulated_conv2d_act', 'demod_coefficients', 'affine_warp_bilinear', 'reflect_pad']

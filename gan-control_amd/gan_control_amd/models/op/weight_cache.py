@@ -31,6 +31,14 @@ weight version is requested it recomputes ALL remembered forms of ALL parameters
 ~4 per layer.  The grouped kernels share their per-element arithmetic with the single-tensor ones: bit-identical values.
 ``GANCONTROL_WEIGHT_BATCH=0`` turns the batching off.
 
+Fused refresh: on the HIP backend the missing forms are first offered to ``refresh_runner`` (op/weight_refresh.py, gc_weight_refresh_grouped_f32):
+every recipe chain that starts at a parameter view [N, K, taps] with 1 or 9 taps -- kernel layout of the view, adjoint layout of that (and of that), the hi / lo
+pack of the first two, wsq of the view -- becomes ONE item of one launch that reads the parameter once and writes all of its forms, instead of one grouped
+launch per level and kind.  ``refresh_with_ema`` (called by trainers/utils.accumulate) runs the generator's refresh in the launches that also
+update the EMA copy.  Anything the kernel does not express (another tap count, an in-major source, a pack of another format, a deeper chain)
+stays on the level-by-level code in the same call.  The values are the same bits either way.  ``GANCONTROL_WEIGHT_REFRESH=0`` turns the fused
+refresh off (the grouped kernels and the foreach EMA run as before); so do ``GANCONTROL_WEIGHT_BATCH=0`` and ``GANCONTROL_WEIGHT_CACHE=0``.
+
 Everything else -- an EMA network updated by somebody else's ``par.data.mul_().add_()`` (the reference's own ``accumulate``,
 trainers/utils.py:8-12), a leaf tensor a caller passes in -- is recomputed on every call.  A root whose storage moved
 (``module.to()``, ``load_state_dict(assign=True)``) is dropped on sight.
@@ -58,6 +66,8 @@ _warned = set()  # kinds of batched refill already reported as unsupported
 stats = {'hit': 0, 'miss': 0, 'bypass': 0, 'batched': 0, 'batch_failed': 0}
 batch_runner = None   # set by op/_backend.py: () -> callable(kind, items) -> [tensor] of the active backend, or None
 pack_wanted = None    # set by op/_backend.py: () -> bool, does the active convolution arithmetic read hi / lo packs at all
+refresh_runner = None # set by op/weight_refresh.py: () -> the runner of the fused refresh (taps, pack_bytes, ema_ok, run) while the HIP backend is active
+                      # and GANCONTROL_WEIGHT_REFRESH is on, else None
 
 
 generation = [0]      # bumped whenever anything is dropped: lets callers keep their own short-cuts over several cached tensors honest
@@ -126,12 +136,8 @@ def _forget(rid):
     _group_of.pop(rid, None)
 
 
-def _refill_group(gid):
-    """Recompute every remembered form of every parameter of group ``gid`` that is missing, level by level (forms of the parameter, forms of
-    those forms, ...), each level's re-layouts in one grouped launch and its packs in another."""
-    run = batch_runner() if batch_runner is not None else None
-    if run is None:
-        return
+def _missing_forms(gid):
+    """[(depth, root id, root, key, recipe)]: every remembered form of every parameter of group ``gid`` that the cache does not hold."""
     todo = []
     for ref in _group_members.get(gid, ()):
         root = ref()
@@ -144,8 +150,175 @@ def _refill_group(gid):
         for key, recipe in _recipes_of(root).items():
             if key not in bucket:
                 todo.append((len(key), id(root), root, key, recipe))
+    return todo
+
+
+def _numel(shape):
+    n = 1
+    for d in shape:
+        n *= d
+    return n
+
+
+def _view_of(root, key):
+    """The contiguous view of the parameter a key starts with: (storage offset, shape)."""
+    off, shape = key[0] - root.storage_offset(), key[1]
+    return root.detach().reshape(-1)[off: off + _numel(shape)].view(shape)
+
+
+def _layout_spec(recipe, taps_ok):
+    """(taps, k, n, flip, scale, w_t shape) of a recipe "parameter view [N, K, taps] -> kernel layout [taps, K, N]" the fused refresh expresses, else None."""
+    if recipe is None or recipe[0] != 'layout':
+        return None
+    _, taps, k, n, src_stride, dst_shape, dst_stride, flip, scale = recipe
+    if taps not in taps_ok or tuple(src_stride) != (1, taps, k * taps) or tuple(dst_stride) != (k * n, n, 1) or _numel(dst_shape) != taps * k * n:
+        return None
+    return taps, k, n, bool(flip), float(scale), tuple(dst_shape)
+
+
+def _adjoint_shape(recipe, taps, k, n):
+    """The shape of adj(w_t) when the recipe is the adjoint layout of a [taps, k, n] kernel layout (taps mirrored, scale 1), else None."""
+    if recipe is None or recipe[0] != 'layout':
+        return None
+    _, t2, k2, n2, src_stride, dst_shape, dst_stride, flip, scale = recipe
+    if (t2, k2, n2) != (taps, k, n) or tuple(src_stride) != (k * n, n, 1) or tuple(dst_stride) != (n * k, 1, k) or not flip or float(scale) != 1.0 \
+            or _numel(dst_shape) != taps * k * n:
+        return None
+    return tuple(dst_shape)
+
+
+def _refresh_plan(todo, runner):
+    """The missing forms the fused refresh can make, as items: one per (parameter view, kernel-layout recipe) with every form of that chain
+    that is missing -- the layout itself, its adjoint layout, the adjoint layout of that, the pack of the first two -- and the view's wsq on the
+    first item of the view (an item of its own where the view has no other form).  -> (items for runner.run, [(item index, form, root id, key)]).  What is not listed stays missing:
+    the level-by-level refill, or the caller's own make(), computes it."""
+    packs = pack_wanted is None or pack_wanted()
+    items, index, owners, wsqs = [], {}, [], []
+
+    def item_of(rid, root, key, spec):
+        chain = (rid, key[:2], key[2] if spec is not None else None)          # the kernel-layout recipe the chain starts with; None: wsq alone
+        at = index.get(chain)
+        if at is None:
+            if spec is None:
+                shape = key[1]
+                spec = (_numel(shape[2:]), shape[1], shape[0], False, 1.0, None)
+            at = index[chain] = len(items)
+            items.append({'src': _view_of(root, key), 'taps': spec[0], 'k': spec[1], 'n': spec[2], 'flip': spec[3], 'scale': spec[4],
+                          'w_t': None, 'adj': None, 'adj2': None, 'pack_w': 0, 'pack_adj': 0, 'wsq': False, 'ema': None, 'root': rid, 'view': key[:2]})
+        return at
+
+    for depth, rid, root, key, recipe in todo:
+        if depth < 3 or depth > 5 or len(key[1]) < 2:
+            continue
+        if depth == 3 and recipe[0] == 'wsq':
+            wsqs.append((rid, root, key))
+            continue
+        spec = _layout_spec(recipe if depth == 3 else _recipes_of(root).get(key[:3]), runner.taps)
+        if spec is None or _numel(key[1]) != spec[0] * spec[1] * spec[2]:
+            continue
+        taps, k, n = spec[:3]
+        if depth == 3:
+            form, want = 'w_t', spec[5]
+        elif depth == 4 and recipe[0] == 'layout':
+            form, want = 'adj', _adjoint_shape(recipe, taps, k, n)
+        elif depth == 4 and recipe[0] == 'pack':
+            form, want = 'pack_w', runner.pack_bytes(recipe[1], taps, k, n) if packs else 0
+        elif depth == 5 and _adjoint_shape(_recipes_of(root).get(key[:4]), taps, k, n) is None:
+            continue
+        elif depth == 5 and recipe[0] == 'pack':
+            form, want = 'pack_adj', runner.pack_bytes(recipe[1], taps, n, k) if packs else 0
+        elif depth == 5 and recipe[0] == 'layout':          # adj(adj(w_t)): the weights of a double-backward convolution, the values of w_t
+            form, want = 'adj2', _adjoint_shape(recipe, taps, n, k)
+        else:
+            continue
+        if not want:
+            continue
+        at = item_of(rid, root, key, spec)
+        items[at][form] = want
+        owners.append((at, form, rid, key))
+    for rid, root, key in wsqs:
+        shape = key[1]
+        if len(shape) != 4 or _numel(shape[2:]) not in runner.taps:
+            continue
+        at = next((i for i, it in enumerate(items) if it['root'] == rid and it['view'] == key[:2]), None)
+        if at is None:
+            at = item_of(rid, root, key, None)
+        elif (items[at]['taps'], items[at]['k'], items[at]['n']) != (_numel(shape[2:]), shape[1], shape[0]):
+            continue
+        items[at]['wsq'] = True
+        owners.append((at, 'wsq', rid, key))
+    return items, owners
+
+
+def _keep(owners, outs):
+    for at, form, rid, key in owners:
+        out = outs[at].get(form)
+        if out is not None and out.numel() > 0 and out.data_ptr() not in _derived:
+            _roots[rid][2][key] = out
+            _derived[out.data_ptr()] = (rid, key)
+            stats['batched'] += 1
+
+
+def _unsupported(kind, e):
+    stats['batch_failed'] += 1
+    if kind not in _warned:
+        _warned.add(kind)
+        warnings.warn('gan_control_amd: batched refill of the %r weight forms is unsupported for this network (%s); '
+                      'falling back to one launch per tensor' % (kind, e))
+
+
+def refresh_with_ema(module, dst, src, decay, alpha):
+    """``dst[i] <- decay * dst[i] + alpha * src[i]`` (the bits of torch._foreach_mul_ / _foreach_add_) over the parameters ``src`` of the registered
+    ``module`` and, in the same launches, every remembered form of those parameters that is missing.  -> True when it ran; False when the fused
+    refresh is not available for these arguments (the caller then runs its own EMA; nothing was written)."""
+    runner = refresh_runner() if (refresh_runner is not None and ENABLED and BATCHED) else None
+    gid = id(module)
+    if runner is None or gid not in _group_members or len(dst) != len(src) or not src:
+        return False
+    live = {id(t) for t in (ref() for ref in _group_members[gid]) if t is not None}
+    if live != {id(p) for p in src}:
+        return False            # not the parameters this module was registered with
+    if not runner.ema_ok([p.detach() for p in src] + list(dst)) or any(d.numel() != p.numel() or d.data_ptr() == p.data_ptr() for d, p in zip(dst, src)):
+        return False
+    items, owners = _refresh_plan(_missing_forms(gid), runner)
+    # the EMA of a parameter rides on the first item that reads the whole of it; every other parameter is a flat item
+    first, flats = {}, []
+    for i, it in enumerate(items):
+        first.setdefault(it['root'], i)
+    for d, p in zip(dst, src):
+        at = first.get(id(p))
+        if at is not None and items[at]['src'].numel() == p.numel() and items[at]['src'].data_ptr() == p.data_ptr():
+            items[at]['ema'] = (d, decay, alpha)
+        else:
+            flats.append((p.detach(), d, decay, alpha))
+    try:
+        outs = runner.run(items, flats)
+    except _lib.UnsupportedError as e:
+        _unsupported('refresh', e)
+        return False
+    _keep(owners, outs)
+    return True
+
+
+def _refill_group(gid):
+    """Recompute every remembered form of every parameter of group ``gid`` that is missing: what the fused refresh expresses in one pass over the
+    parameters (module docstring), the rest level by level (forms of the parameter, forms of those forms, ...), each level's re-layouts in one
+    grouped launch and its packs in another."""
+    run = batch_runner() if batch_runner is not None else None
+    if run is None:
+        return
+    todo = _missing_forms(gid)
     if len(todo) < 2:
         return
+    runner = refresh_runner() if refresh_runner is not None else None
+    if runner is not None:
+        items, owners = _refresh_plan(todo, runner)
+        if items:
+            try:
+                _keep(owners, runner.run(items))
+            except _lib.UnsupportedError as e:
+                _unsupported('refresh', e)
+            todo = [t for t in todo if t[3] not in _roots[t[1]][2]]
     for depth in sorted({t[0] for t in todo}):
         level = [t for t in todo if t[0] == depth]
         for kind in ('layout', 'pack', 'wsq'):

@@ -72,10 +72,14 @@ def accumulate(model1, model2, decay=0.999):
     source = dict(named_params(model2))
     names = sorted(target)
     dst = [target[n].data for n in names]
-    src = [source[n].data for n in names]
-    torch._foreach_mul_(dst, decay)
-    torch._foreach_add_(dst, src, alpha=1 - decay)
     from ..models.op import weight_cache
+    # on the HIP backend, for a network registered with the cache: the EMA and the refresh of model2's derived weight forms in the same launches,
+    # each parameter read once (op/weight_refresh.py; the same bits as the two foreach kernels).  The forms are invalid at this point in the
+    # trainer -- accumulate follows the generator's last optimiser step of the iteration -- and the generator does not change before its next forward
+    if not (len(source) == len(names) and weight_cache.refresh_with_ema(model2, dst, [source[n] for n in names], decay, 1 - decay)):
+        src = [source[n].data for n in names]
+        torch._foreach_mul_(dst, decay)
+        torch._foreach_add_(dst, src, alpha=1 - decay)
     weight_cache.invalidate(target.values())       # ``.data`` writes do not bump the version counters the cache of derived weight forms is keyed on
 
 

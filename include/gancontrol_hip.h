@@ -483,6 +483,41 @@ typedef struct gc_wpack_group {
 } gc_wpack_group;
 int gc_conv2d_pack_weights_bf16x3_grouped(const gc_wpack_group* groups, int n_groups, gc_stream_t stream);
 
+/* One pass per parameter for everything between an optimiser step and the next forward pass: the EMA copy and every derived form of a
+ * convolution weight, each parameter read once.  Two kinds of item share the table:
+ *   weight item (taps = 1 or 9)   src: the parameter [n, k, taps], taps fastest.  Every output is optional (NULL = not wanted):
+ *     ema       [n, k, taps]   ema = decay * ema + alpha * src in place: the bits of torch._foreach_mul_(ema, decay) followed by
+ *                              torch._foreach_add_(ema, src, alpha=alpha), both scalars rounded to float once
+ *     w_t       [taps, k, n]   scale * src, taps mirrored if flip_taps                        (gc_weight_layout_f32, parameter -> kernel layout)
+ *     adj       [taps, n, k]   adj[taps - 1 - t][n][k] = w_t[t][k][n]                         (gc_weight_layout_f32, the adjoint layout)
+ *     adj2      [taps, k, n]   adj(adj): the values of w_t in a tensor of its own (the weights of a double-backward convolution)
+ *     pack_w    hi / lo packs of w_t, the format and size of gc_conv2d_pack_weights_bf16x3 for in_ch = k, out_ch = n: 2 * taps *
+ *               ceil(k / 8) * n units of 16 bytes, 16-byte aligned
+ *     pack_adj  the same of adj (in_ch = n, out_ch = k)
+ *     wsq       [n, k]         sum over the taps of src^2                                     (gc_weight_sq_grouped_f32)
+ *   flat item (taps = 0)          src, ema: count floats; the EMA only.  n, k and the form pointers are unused (NULL).
+ * Every value is bit-identical to the entry named next to it.  src is only read.  Outputs must not overlap src or each other.
+ * Any other tap count returns GC_ERR_UNSUPPORTED, null or non-positive operands GC_ERR_BAD_ARG; everything is checked before the first
+ * launch.  The table is cut into as many launches as its items need (16 weight items and 76 flat items each).
+ * gc_weight_refresh_launches: kernel launches the entry has issued in this process so far (tests count the launches of a refresh with it).
+ * gc_weight_refresh_item_bytes: sizeof(gc_wrefresh_item) of the built library (the binding compares it with its mirror). */
+typedef struct gc_wrefresh_item {
+    const float* src;
+    float* ema;
+    float* w_t;
+    float* adj;
+    float* adj2;
+    void* pack_w;
+    void* pack_adj;
+    float* wsq;
+    int64_t count;
+    int32_t n, k, taps, flip_taps;
+    float scale, decay, alpha;
+} gc_wrefresh_item;
+int gc_weight_refresh_grouped_f32(const gc_wrefresh_item* items, int n_items, gc_stream_t stream);
+int64_t gc_weight_refresh_launches(void);
+size_t gc_weight_refresh_item_bytes(void);
+
 /* The backward of a fused (k <= 3 -> n) 1x1 convolution + bias + leaky-ReLU -- the discriminator's FromRGB ConvLayer (gan_model.py:955,
  * 844-890), whose output [B, 32, 1024, 1024] is the largest activation of D -- without a separate activation-backward pass: the gradient dy
  * that arrives at the activation output is multiplied by the mask (y_ref > 0 ? gain : gain * slope) while it is loaded.
