@@ -158,6 +158,9 @@ SIGNATURES = {
     'gc_weight_refresh_grouped_f32': (_i32, [ctypes.POINTER(WRefreshItem), _i32, _vp]),
     'gc_weight_refresh_launches': (_i64, []),
     'gc_weight_refresh_item_bytes': (_sz, []),
+    'gc_group_moments_workspace': (_sz, [_i32, _vp, _vp, _i32]),
+    'gc_group_moments_f32': (_i32, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
+    'gc_group_project_f32': (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
 }
 
 _lib = None

@@ -12,6 +12,7 @@ of this one: ``generate_matrix_by_group``, ``interpolate_by_group``, ``slerp``, 
 import json
 import os
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -61,9 +62,10 @@ class Inference:
         return self.model.input.input.dtype          # what latents and noise maps are drawn in (float32 unless the model was converted)
 
     # -- w space ----------------------------------------------------------------------------------------------------------------------
-    def style(self, latent_z):
+    def style(self, latent_z, out=None):
         """``model.style(latent_z)`` as one ``fc_stacks_forward`` call: every group's mapping stack reads its slice of z and writes its
-        slice of w (no cat); the plain 512-wide stack of a vanilla model is one stack over whole rows."""
+        slice of w (no cat); the plain 512-wide stack of a vanilla model is one stack over whole rows.  ``out``: a [B, style_dim] tensor
+        (rows of adjacent elements, e.g. a row range of a larger buffer) to write w into; it is returned."""
         style = self.model.style
         if isinstance(style, MultiFcStack):
             names = style.fc_config.in_order_group_names
@@ -72,8 +74,9 @@ class Inference:
         elif isinstance(style, nn.Sequential) and len(style) > 1 and isinstance(style[0], PixelNorm):
             stacks, slices = [style], [None]
         else:
-            return style(latent_z)                     # marge_fc: two stages, left to the modules
-        latent_w = torch.empty(latent_z.shape[0], self.model.style_dim, dtype=latent_z.dtype, device=latent_z.device)
+            w = style(latent_z)                        # marge_fc: two stages, left to the modules
+            return w if out is None else out.copy_(w)
+        latent_w = out if out is not None else torch.empty(latent_z.shape[0], self.model.style_dim, dtype=latent_z.dtype, device=latent_z.device)
         return fc_stacks_forward(stacks, latent_z, slices, latent_w, slices)
 
     def _places(self):
@@ -180,12 +183,40 @@ class Inference:
         so = torch.sin(omega)
         return (torch.sin((1.0 - val) * omega) / so).unsqueeze(1) * low + (torch.sin(val * omega) / so).unsqueeze(1) * high
 
-    def gen_grid_image_from_latent(self, latent, noise=None, nrow=4, downsample=None):
-        """The PIL grid of ``self.model([latent], noise=noise)`` (a z latent), ``nrow`` images per row."""
+    def gen_grid_image_from_latent(self, latent, noise=None, nrow=4, downsample=None, input_is_latent=False):
+        """The PIL grid of ``self.model([latent], noise=noise)`` (a z latent; a w latent with ``input_is_latent=True``), ``nrow`` images per
+        row."""
         from ..evaluation.image_grid import grid_image
         with torch.no_grad():
-            sample, _ = self.model([latent.to(self.device)], noise=noise)
+            sample, _ = self.model([latent.to(self.device)], noise=noise, input_is_latent=input_is_latent)
         return grid_image(sample, nrow=nrow, downsample=downsample)
+
+    @torch.no_grad()
+    def generate_matrix_by_pca(self, group, pca, n_components=6, sigmas=(-2, -1, 0, 1, 2), latent=None, save_path=None, downsample=None,
+                               generator=None):
+        """The per-group traversal picture of a ``GroupPCA`` (projection/pca.py): image (k, c) renders the w latent with ``group``'s slice
+        moved by ``sigmas[c] * sqrt(explained_variance[k]) * components[k]``, for the first ``n_components`` retained components (fewer
+        where fewer were kept).  ``latent``: a w latent [D] or [1, D]; None draws z (from ``generator`` when one is given) and maps it.  One
+        static noise for every image; all rows go through ONE ``gen_grid_image_from_latent`` call, ``len(sigmas)`` images per row; saved to
+        ``'%s.jpg' % save_path`` when a path is given.  -> the PIL image."""
+        from ..evaluation.generation import _randn
+        if group not in pca.components:
+            raise ValueError('generate_matrix_by_pca: group %r is not in the fit (groups: %s)' % (group, list(pca.components)))
+        lo, hi = pca.places[group]
+        comps = pca.components[group]
+        rows = min(int(n_components), comps.shape[0])
+        if latent is None:
+            latent = self.style(_randn((1, self.config.model_config['latent_size']), self.device, generator).to(self._dtype()))
+        w = latent.to(self.device, self._dtype()).reshape(1, -1)
+        ev = pca.explained_variance[group]
+        steps = torch.tensor([[float(s) * float(np.sqrt(ev[k])) for s in sigmas] for k in range(rows)], dtype=w.dtype, device=self.device)
+        moved = w.repeat(rows * len(sigmas), 1)
+        moved[:, lo:hi] += (steps[:, :, None] * comps[:rows, None, :].to(w.dtype)).reshape(-1, hi - lo)          # row k * len(sigmas) + c
+        self.reset_noise(generator)
+        image = self.gen_grid_image_from_latent(moved, noise=self.noise, nrow=len(sigmas), downsample=downsample, input_is_latent=True)
+        if save_path is not None:
+            image.save('%s.jpg' % save_path)
+        return image
 
     def generate_matrix_by_group(self, group, save_path=None, downsample=None, generator=None):
         """The 6 x 6 matrix in which image (row, col) carries ``group``'s slice of sample ``row`` and the rest of sample ``col``, one shared

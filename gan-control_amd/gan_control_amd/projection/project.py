@@ -15,6 +15,7 @@ from torch import nn
 from ..datasets import image_ops
 from ..evaluation import image_grid
 from .noise_ops import noise_normalize_, noise_regularize
+from .pca import GroupPCA, model_places
 
 
 def get_lr(t, initial_lr, rampdown=0.25, rampup=0.05):
@@ -82,7 +83,7 @@ def load_source_images(images, res=256, device=None):
 
 
 def project(model, target, /, *, steps=1000, lr=0.1, noise=0.05, noise_ramp=0.75, noise_regularize_weight=1e5, mse_weight=0.0, percept=None,
-            w_plus=False, n_mean_latent=10000, optimize_noise=True, generator=None, on_step=None):
+            w_plus=False, n_mean_latent=10000, optimize_noise=True, generator=None, on_step=None, pca=None):
     """Optimise a latent and the per-layer noise maps until ``model`` (a Generator; positional) reproduces ``target`` [B, 3, size, size].
 
     Every step i of ``steps`` (t = i / steps): Adam's learning rate is ``get_lr(t, lr)``; the latent is perturbed by ``latent_noise`` of
@@ -91,6 +92,10 @@ def project(model, target, /, *, steps=1000, lr=0.1, noise=0.05, noise_ramp=0.75
     percept: any callable (img, target) -> tensor (an LPIPS network stays external); None with mse_weight == 0 is an error.  w_plus: one
     latent per layer.  optimize_noise=False keeps the drawn maps fixed.  generator: a torch.Generator for every draw made here.
     on_step(i, info): called after each step with the tensors of that step (loss, mse, percept, noise_loss, lr, latent, noises).
+    pca: None, a ``GroupPCA`` (projection/pca.py) or a float variance share -- then a ``GroupPCA`` is fitted on the ``n_mean_latent`` draws
+    made here, over the groups of the model's fc_config when the mapping network is split and over the whole row otherwise.  When given,
+    ``pca.project_(latent)`` keeps the latent in the retained per-group subspaces after every optimiser step (before the noise maps are
+    re-normalised), so the returned latent is projected.  ``pca=None`` launches exactly what the loop launched before the option existed.
 
     The model's parameters get requires_grad_(False) for the duration and their flags back afterwards.
     -> (latent, noises, image, history): the optimised latent [B, style_dim] ([B, n_latent, style_dim] with w_plus), the noise maps, the
@@ -115,6 +120,10 @@ def project(model, target, /, *, steps=1000, lr=0.1, noise=0.05, noise_ramp=0.75
             latent_mean = latent_out.mean(0)
             latent_std = ((latent_out - latent_mean).pow(2).sum() / n_mean_latent) ** 0.5
             noises = [randn(*n.shape) for n in model.make_noise(batch, device=dev)]
+            if pca is not None and not isinstance(pca, GroupPCA):
+                pca = GroupPCA.fit(latent_out, model_places(model), float(pca))
+        if pca is not None and pca.mean.device != latent_out.device:
+            raise ValueError('project: the GroupPCA lives on %s, the latent on %s; fit it on the target\'s device' % (pca.mean.device, latent_out.device))
         latent_in = latent_mean.detach().clone().unsqueeze(0).repeat(batch, 1)
         if w_plus:
             latent_in = latent_in.unsqueeze(1).repeat(1, model.n_latent, 1)
@@ -137,6 +146,8 @@ def project(model, target, /, *, steps=1000, lr=0.1, noise=0.05, noise_ramp=0.75
             optimizer.zero_grad()
             loss.backward()
             optimizer.step()
+            if pca is not None:
+                pca.project_(latent_in)
             if optimize_noise:
                 noise_normalize_(noises)
             rec = {'loss': loss.detach(), 'mse': mse.detach(), 'percept': p_loss.detach(), 'noise_loss': n_loss.detach(), 'lr': step_lr}

@@ -853,6 +853,42 @@ int gc_latent_interp_f32(const float* fixed, int64_t fixed_stride, const float* 
 int gc_noise_blend_f32(const float* const* a, const float* const* b, float* const* out, const int64_t* counts, int n, float wa, float wb,
                        gc_stream_t stream);
 
+/* ---- per-group latent PCA (projection/pca.py through models/op/group_pca.py, csrc/group_pca.hip) ------------------------------------------
+ * A group table is two HOST arrays lo, hi of `groups` int32: group g is the columns [lo[g], hi[g]) of a row, width D_g = hi[g] - lo[g].
+ * Limits: 1 <= groups <= GC_GROUP_MAX, 1 <= D_g <= GC_GROUP_MAX_WIDTH, hi[g] <= stride; n * stride must fit an int64.
+ *
+ * gc_group_moments_f32: w: DEVICE float32 [n, stride] (row r at w + r * stride, stride in ELEMENTS, any 4-byte alignment), 2 <= n <=
+ * GC_GROUP_MAX_ROWS.  mean: DEVICE float64 [sum D_g] and cov: DEVICE float64 [sum D_g^2], both packed group after group in table order; cov
+ * of a group is a full row-major symmetric D_g x D_g matrix with divisor n - 1 (scikit-learn's explained_variance_ convention):
+ *   mean[g][i] = S1_i / n,   cov[g][i, j] = (S2_ij - S1_a S1_c / n) / (n - 1),   (a, c) = (min(i, j), max(i, j)),
+ * S1 = sum_r x_r and S2 = sum_r x_r x_r^T over the group's columns, values widened to float64 on load, products exact, sums in float64 over
+ * splits of R = GC_GROUP_ROW_SPLIT rows in ascending row order -- R = 16 * ceil(ceil(n / GC_GROUP_MAX_SPLITS) / 16) where n / GC_GROUP_ROW_SPLIT
+ * would make more than GC_GROUP_MAX_SPLITS splits --, the splits' partial sums added in ascending order by a second launch of the same call.  cov[g][i, j] and cov[g][j, i] are the same bits; no atomics: the same inputs give the same bits on every run.  Only tiles on or above
+ * the diagonal are computed.  No byte outside the D_g columns of the n rows of each group is loaded (columns of no group are never read);
+ * 16-byte loads where w is 16-byte aligned, stride % 4 == 0 and lo[g] % 4 == 0, 4-byte loads otherwise: both stage the same values.  Only
+ * mean, cov and the workspace are stored.  Workspace: gc_group_moments_workspace(n, lo, hi, groups) bytes = ceil(n / R) * (sum D_g +
+ * sum D_g^2) * 8, at most GC_GROUP_MAX_SPLITS partial sets (0 for arguments outside the limits).  Null pointers, n < 2, an empty group or one outside the stride return
+ * GC_ERR_BAD_ARG, more than GC_GROUP_MAX groups, a group wider than GC_GROUP_MAX_WIDTH or more than GC_GROUP_MAX_ROWS rows
+ * GC_ERR_UNSUPPORTED, a short workspace GC_ERR_WORKSPACE; nothing is launched then.
+ *
+ * gc_group_project_f32: in place, for every row r < rows of x (DEVICE float32, row r at x + r * stride) and every group:
+ *   x_g <- m_g + P_g^T (P_g (x_g - m_g))
+ * with m_g = mean[lo[g] .. hi[g]) (DEVICE float32, indexed by column) and P_g = components[g] (a HOST array of DEVICE pointers to dense
+ * float32 [ranks[g], D_g] matrices, 1 <= ranks[g] <= D_g).  float32 arithmetic in a fixed order: d = fl(x - m); c_k = sum over columns in
+ * ascending steps of 64 (fused multiply-adds) and a fixed butterfly over the 64 partial sums; y_j = fused multiply-adds over k ascending,
+ * then fl(m_j + y_j).  Columns outside every group keep their bits; one launch.  Null pointers, rows < 1, ranks outside [1, D_g], groups
+ * that overlap and the group-table errors above return GC_ERR_BAD_ARG / GC_ERR_UNSUPPORTED; nothing is launched then. */
+#define GC_GROUP_MAX 16
+#define GC_GROUP_MAX_WIDTH 512
+#define GC_GROUP_ROW_SPLIT 256
+#define GC_GROUP_MAX_SPLITS 64
+#define GC_GROUP_MAX_ROWS (65535 * GC_GROUP_ROW_SPLIT)
+size_t gc_group_moments_workspace(int n, const int32_t* lo, const int32_t* hi, int groups);
+int gc_group_moments_f32(const float* w, int64_t stride, int n, const int32_t* lo, const int32_t* hi, int groups, double* mean, double* cov,
+                         void* workspace, size_t workspace_bytes, gc_stream_t stream);
+int gc_group_project_f32(float* x, int64_t stride, int rows, const float* mean, const float* const* components, const int32_t* ranks,
+                         const int32_t* lo, const int32_t* hi, int groups, gc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
