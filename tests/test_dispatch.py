@@ -283,6 +283,49 @@ def test_every_step_conv_variant_has_a_kernel_case():
     assert step <= cases, sorted(step - cases)
 
 
+_MODE_IDS = {'f32': 0, 'bf16x3': 1, 'bf16': 2}
+
+
+def _frozen_names(column):
+    """The kernel names (split plan stripped) of one probe column of tests/golden/dispatch_table.json over all its geometry groups; rc* cells (no kernel) skipped."""
+    import json
+    sys.path.insert(0, os.path.join(REPO, 'tools'))
+    import dispatch_table
+    with open(dispatch_table.GOLDEN) as f:
+        frozen = json.load(f)
+    return {n for group, g in frozen.items() if group.split('|', 1)[1] == column for n in g.get('names', {}) if not n.startswith('rc')}
+
+
+def _conv_name(case, mode):
+    b, K, N, h, w, k, up, down, pad = case
+    return _kernel(conv_variant(ConvGeom(k, k, up, down, pad, pad, _out(h, k, up, down, pad), _out(w, k, up, down, pad)), N, b, K, mode, (h, w)))
+
+
+@pytest.mark.parametrize('mode', ['f32', 'bf16x3', 'bf16'])
+def test_every_frozen_variant_has_a_kernel_case(mode):
+    """Every kernel variant of the frozen decision table is compared with fp64 at kernel level (tests/test_ops_gpu.py) in each arithmetic: the forward
+    variants by the forward lists (test_conv2d_kernel, test_conv2d_bf16x3_kernel, test_conv2d_bf16_kernel, test_conv2d_variants) and again by the fused
+    epilogue's, the weight-gradient variants by WGRAD_VARIANT_CASES, the per-sample ones by SAMPLE_WGRAD_CASES.  test_dispatch_table_matches_the_frozen_digest
+    ties the table to the built library, so a new variant cannot ship without a case."""
+    import test_ops_gpu as ops
+    forward = {'f32': ops.CONV_CASES + ops.SMALL_CASES, 'bf16x3': ops.BF16_CASES, 'bf16': ops.BF16_CASES[::3]}[mode] + [c[0] for c in ops.CONV_VARIANT_CASES]
+    conv = _frozen_names('conv_variant[mode=%d]' % _MODE_IDS[mode])
+    wgrad = {_kernel(_wprobe(b, K, N, h, k, down, pad, mode=mode, w=w)) for (b, K, N, h, w, k, down, pad, _), _, _ in ops.WGRAD_VARIANT_CASES}
+    samples = set()
+    for b, K, N, h, w, k, down, pad, _, _ in ops.SAMPLE_WGRAD_CASES:
+        try:
+            samples.add(_kernel(_wprobe(b, K, N, h, k, down, pad, samples=True, mode=mode, w=w)))
+        except RuntimeError:
+            assert mode == 'f32', 'the split-bf16 arithmetics have a per-sample form for every shape of the list'
+    missing = {
+        'forward lists': conv - {_conv_name(c, mode) for c in forward},
+        'EPILOGUE_CASES': conv - {_conv_name(c, mode) for c in ops.EPILOGUE_CASES},
+        'WGRAD_VARIANT_CASES': _frozen_names('wgrad_variant[mode=%d,samples=0]' % _MODE_IDS[mode]) - wgrad,
+        'SAMPLE_WGRAD_CASES': _frozen_names('wgrad_variant[mode=%d,samples=1]' % _MODE_IDS[mode]) - samples,
+    }
+    assert not any(missing.values()), 'variants of the frozen table no %s case reaches: %s' % (mode, {k: sorted(v) for k, v in missing.items() if v})
+
+
 @pytest.mark.parametrize('out_h,out_w,prefix', [(40, 33, 'conv_bf16x3_kernel<1,4,2,1>|up1,down2'), (33, 33, 'conv_s2ws_bf16x3_kernel<1>'),
                                                 (33, 40, 'conv_bf16x3_kernel<1,4,2,1>|up1,down2')])
 def test_unmasked_stride2_kernel_takes_only_outputs_that_read_inside_the_plane(out_h, out_w, prefix):

@@ -581,14 +581,183 @@ def test_conv2d_bf16x3_kernel(case, bf16x3_mode):
             assert rel_err(out, ref) < 5e-5, ('wgrad', use_scales)
 
 
+# the kernels that compute in exact fp32 whatever the mode (every mode sends what the bf16 MFMA kernels do not take to them) and the bf16 MFMA families
+_EXACT_FP32 = ('conv_mfma_kernel', 'conv_f32_small_kernel', 'pw_narrow_kernel', 'pw_widen_kernel')
+_BF16_FAMILIES = ('conv_bf16x3_', 'conv_s2ws_', 'convt_fused_', 'convt_bf16x3_')
+
+
+def _conv_tol(name, mode):
+    """Bound against fp64 by the kernel family a launch reaches: 5e-6 exact fp32 in every mode, 5e-5 split-bf16, 2e-2 plain bf16 (as everywhere in this file)."""
+    if name.startswith(_EXACT_FP32):
+        return 5e-6
+    assert name.startswith(_BF16_FAMILIES) and mode != 'f32', (name, mode)
+    return {'bf16x3': 5e-5, 'bf16': 2e-2}[mode]
+
+
+CONV_VARIANT_CASES = [
+    # (b, K, N, h, w, k, up, down, pad), the variant gc_conv2d_variant_name names in split-bf16, in plain bf16 and in exact fp32 (names frozen from the built
+    # library): every forward variant of tests/golden/dispatch_table.json that CONV_CASES + SMALL_CASES (fp32), BF16_CASES (split-bf16) and BF16_CASES[::3]
+    # (plain bf16) do not reach -- tests/test_dispatch.py::test_every_frozen_variant_has_a_kernel_case.  Each is ragged on a tiled axis: out_w off the pixel
+    # tile, odd planes, N outside the output-channel block.
+    # conv_mfma_kernel<2,2,1,8,2,2,32> (the exact-fp32 step's main kernel) in its six geometries: 3 -> 72 channels, out_w 33 / 39 / 65
+    ((8, 3, 72, 128, 33, 3, 1, 1, 1), 'conv_mfma_kernel<2,2,1,8,2,2,32>|up1,down1,k3', 'conv_mfma_kernel<2,2,1,8,2,2,32>|up1,down1,k3', 'conv_mfma_kernel<2,2,1,8,2,2,32>|up1,down1,k3'),
+    ((8, 3, 72, 128, 33, 1, 1, 1, 0), 'conv_mfma_kernel<2,2,1,8,2,2,32>|up1,down1,k1', 'conv_mfma_kernel<2,2,1,8,2,2,32>|up1,down1,k1', 'conv_mfma_kernel<2,2,1,8,2,2,32>|up1,down1,k1'),
+    ((8, 3, 72, 256, 80, 3, 1, 2, 0), 'conv_mfma_kernel<2,2,1,8,2,2,32>|up1,down2,k3', 'conv_mfma_kernel<2,2,1,8,2,2,32>|up1,down2,k3', 'conv_mfma_kernel<2,2,1,8,2,2,32>|up1,down2,k3'),
+    ((8, 3, 72, 256, 65, 1, 1, 2, 0), 'conv_mfma_kernel<2,2,1,8,2,2,32>|up1,down2,k1', 'conv_mfma_kernel<2,2,1,8,2,2,32>|up1,down2,k1', 'conv_mfma_kernel<2,2,1,8,2,2,32>|up1,down2,k1'),
+    ((2, 3, 72, 128, 32, 3, 2, 1, 2), 'conv_mfma_kernel<2,2,1,8,2,2,32>|up2,down1,k3', 'conv_mfma_kernel<2,2,1,8,2,2,32>|up2,down1,k3', 'conv_mfma_kernel<2,2,1,8,2,2,32>|up2,down1,k3'),
+    ((2, 3, 72, 128, 33, 1, 2, 1, 0), 'conv_mfma_kernel<2,2,1,8,2,2,32>|up2,down1,k1', 'conv_mfma_kernel<2,2,1,8,2,2,32>|up2,down1,k1', 'conv_mfma_kernel<2,2,1,8,2,2,32>|up2,down1,k1'),
+    # the narrow conv_mfma_kernel forms (3 output channels: 4-, 8- and 16-pixel columns; 40 and 72 channels on the small grids): 1x1, transposed 1x1 and 3x3, stride 2
+    ((1, 3, 3, 4, 4, 1, 1, 1, 0), 'conv_mfma_kernel<1,1,4,32,1,1,4>|up1,down1,k1', 'conv_mfma_kernel<1,1,4,32,1,1,4>|up1,down1,k1', 'conv_mfma_kernel<1,1,4,32,1,1,4>|up1,down1,k1'),
+    ((1, 3, 3, 4, 4, 1, 1, 2, 0), 'conv_mfma_kernel<1,1,4,32,1,1,4>|up1,down2,k1', 'conv_mfma_kernel<1,1,4,32,1,1,4>|up1,down2,k1', 'conv_mfma_kernel<1,1,4,32,1,1,4>|up1,down2,k1'),
+    ((1, 3, 3, 4, 4, 1, 2, 1, 0), 'conv_mfma_kernel<1,1,4,32,1,1,4>|up2,down1,k1', 'conv_mfma_kernel<1,1,4,32,1,1,4>|up2,down1,k1', 'conv_mfma_kernel<1,1,4,32,1,1,4>|up2,down1,k1'),
+    ((1, 3, 3, 4, 4, 3, 2, 1, 1), 'conv_mfma_kernel<1,1,4,32,1,1,4>|up2,down1,k3', 'conv_mfma_kernel<1,1,4,32,1,1,4>|up2,down1,k3', 'conv_mfma_kernel<1,1,4,32,1,1,4>|up2,down1,k3'),
+    ((1, 3, 3, 7, 7, 1, 1, 1, 0), 'conv_mfma_kernel<1,1,4,32,1,1,8>|up1,down1,k1', 'conv_mfma_kernel<1,1,4,32,1,1,8>|up1,down1,k1', 'conv_mfma_kernel<1,1,4,32,1,1,8>|up1,down1,k1'),
+    ((1, 3, 3, 6, 7, 3, 1, 1, 0), 'conv_mfma_kernel<1,1,4,32,1,1,8>|up1,down1,k3', 'conv_mfma_kernel<1,1,4,32,1,1,8>|up1,down1,k3', 'conv_mfma_kernel<1,1,4,32,1,1,8>|up1,down1,k3'),
+    ((1, 3, 3, 13, 13, 1, 1, 2, 0), 'conv_mfma_kernel<1,1,4,32,1,1,8>|up1,down2,k1', 'conv_mfma_kernel<1,1,4,32,1,1,8>|up1,down2,k1', 'conv_mfma_kernel<1,1,4,32,1,1,8>|up1,down2,k1'),
+    ((1, 3, 3, 15, 13, 3, 1, 2, 0), 'conv_mfma_kernel<1,1,4,32,1,1,8>|up1,down2,k3', 'conv_mfma_kernel<1,1,4,32,1,1,8>|up1,down2,k3', 'conv_mfma_kernel<1,1,4,32,1,1,8>|up1,down2,k3'),
+    ((1, 3, 3, 7, 7, 1, 2, 1, 0), 'conv_mfma_kernel<1,1,4,32,1,1,8>|up2,down1,k1', 'conv_mfma_kernel<1,1,4,32,1,1,8>|up2,down1,k1', 'conv_mfma_kernel<1,1,4,32,1,1,8>|up2,down1,k1'),
+    ((1, 3, 3, 4, 5, 3, 2, 1, 2), 'conv_mfma_kernel<1,1,4,32,1,1,8>|up2,down1,k3', 'conv_mfma_kernel<1,1,4,32,1,1,8>|up2,down1,k3', 'conv_mfma_kernel<1,1,4,32,1,1,8>|up2,down1,k3'),
+    ((1, 3, 3, 9, 13, 1, 1, 1, 0), 'conv_mfma_kernel<1,1,4,32,1,1,16>|up1,down1,k1', 'conv_mfma_kernel<1,1,4,32,1,1,16>|up1,down1,k1', 'conv_mfma_kernel<1,1,4,32,1,1,16>|up1,down1,k1'),
+    ((1, 3, 3, 9, 13, 3, 1, 1, 1), 'conv_mfma_kernel<1,1,4,32,1,1,16>|up1,down1,k3', 'conv_mfma_kernel<1,1,4,32,1,1,16>|up1,down1,k3', 'conv_mfma_kernel<1,1,4,32,1,1,16>|up1,down1,k3'),
+    ((1, 3, 3, 17, 27, 1, 1, 2, 0), 'conv_mfma_kernel<1,1,4,32,1,1,16>|up1,down2,k1', 'conv_mfma_kernel<1,1,4,32,1,1,16>|up1,down2,k1', 'conv_mfma_kernel<1,1,4,32,1,1,16>|up1,down2,k1'),
+    ((1, 3, 3, 17, 27, 3, 1, 2, 0), 'conv_mfma_kernel<1,1,4,32,1,1,16>|up1,down2,k3', 'conv_mfma_kernel<1,1,4,32,1,1,16>|up1,down2,k3', 'conv_mfma_kernel<1,1,4,32,1,1,16>|up1,down2,k3'),
+    ((1, 3, 3, 9, 13, 1, 2, 1, 0), 'conv_mfma_kernel<1,1,4,32,1,1,16>|up2,down1,k1', 'conv_mfma_kernel<1,1,4,32,1,1,16>|up2,down1,k1', 'conv_mfma_kernel<1,1,4,32,1,1,16>|up2,down1,k1'),
+    ((1, 3, 3, 8, 13, 3, 2, 1, 2), 'conv_mfma_kernel<1,1,4,32,1,1,16>|up2,down1,k3', 'conv_mfma_kernel<1,1,4,32,1,1,16>|up2,down1,k3', 'conv_mfma_kernel<1,1,4,32,1,1,16>|up2,down1,k3'),
+    ((1, 3, 3, 17, 19, 1, 2, 1, 0), 'conv_mfma_kernel<1,4,1,8,1,4,32>|up2,down1,k1', 'conv_mfma_kernel<1,4,1,8,1,4,32>|up2,down1,k1', 'conv_mfma_kernel<1,4,1,8,1,4,32>|up2,down1,k1'),
+    ((1, 3, 3, 16, 19, 3, 2, 1, 2), 'conv_mfma_kernel<1,4,1,8,1,4,32>|up2,down1,k3', 'conv_mfma_kernel<1,4,1,8,1,4,32>|up2,down1,k3', 'conv_mfma_kernel<1,4,1,8,1,4,32>|up2,down1,k3'),
+    ((1, 3, 40, 17, 19, 1, 1, 1, 0), 'conv_mfma_kernel<1,4,1,8,2,2,32>|up1,down1,k1', 'conv_mfma_kernel<1,4,1,8,2,2,32>|up1,down1,k1', 'conv_mfma_kernel<1,4,1,8,2,2,32>|up1,down1,k1'),
+    ((1, 3, 40, 17, 19, 3, 1, 1, 1), 'conv_mfma_kernel<1,4,1,8,2,2,32>|up1,down1,k3', 'conv_mfma_kernel<1,4,1,8,2,2,32>|up1,down1,k3', 'conv_mfma_kernel<1,4,1,8,2,2,32>|up1,down1,k3'),
+    ((1, 3, 40, 5, 17, 1, 2, 1, 0), 'conv_mfma_kernel<1,4,1,8,2,2,32>|up2,down1,k1', 'conv_mfma_kernel<1,4,1,8,2,2,32>|up2,down1,k1', 'conv_mfma_kernel<1,4,1,8,2,2,32>|up2,down1,k1'),
+    ((1, 3, 40, 16, 19, 3, 2, 1, 2), 'conv_mfma_kernel<1,4,1,8,2,2,32>|up2,down1,k3', 'conv_mfma_kernel<1,4,1,8,2,2,32>|up2,down1,k3', 'conv_mfma_kernel<1,4,1,8,2,2,32>|up2,down1,k3'),
+    ((1, 3, 72, 17, 19, 1, 1, 1, 0), 'conv_mfma_kernel<2,2,1,8,1,1,32>|up1,down1,k1', 'conv_mfma_kernel<2,2,1,8,1,1,32>|up1,down1,k1', 'conv_mfma_kernel<2,2,1,8,1,1,32>|up1,down1,k1'),
+    ((1, 3, 72, 17, 19, 3, 1, 1, 1), 'conv_mfma_kernel<2,2,1,8,1,1,32>|up1,down1,k3', 'conv_mfma_kernel<2,2,1,8,1,1,32>|up1,down1,k3', 'conv_mfma_kernel<2,2,1,8,1,1,32>|up1,down1,k3'),
+    ((1, 3, 3, 9, 33, 1, 1, 2, 0), 'conv_mfma_kernel<2,2,1,8,1,1,32>|up1,down2,k1', 'conv_mfma_kernel<2,2,1,8,1,1,32>|up1,down2,k1', 'conv_mfma_kernel<2,2,1,8,1,1,32>|up1,down2,k1'),
+    ((1, 3, 3, 63, 65, 3, 1, 2, 0), 'conv_mfma_kernel<2,2,1,8,1,1,32>|up1,down2,k3', 'conv_mfma_kernel<2,2,1,8,1,1,32>|up1,down2,k3', 'conv_mfma_kernel<2,2,1,8,1,1,32>|up1,down2,k3'),
+    ((1, 3, 72, 5, 17, 1, 2, 1, 0), 'conv_mfma_kernel<2,2,1,8,1,1,32>|up2,down1,k1', 'conv_mfma_kernel<2,2,1,8,1,1,32>|up2,down1,k1', 'conv_mfma_kernel<2,2,1,8,1,1,32>|up2,down1,k1'),
+    # conv_f32_small_kernel: 1x1 at stride 1 and 2, a 1x1 batch of two, the transposed 3x3 onto 9 x 9, stride 2 onto 8 x 8
+    ((1, 64, 64, 4, 4, 1, 1, 1, 0), 'conv_f32_small_kernel<1,2,1,1>|up1,down1,k1', 'conv_f32_small_kernel<1,2,1,1>|up1,down1,k1', 'conv_f32_small_kernel<1,2,1,1>|up1,down1,k1'),
+    ((1, 64, 64, 4, 4, 1, 1, 2, 0), 'conv_f32_small_kernel<1,2,1,2>|up1,down2,k1', 'conv_f32_small_kernel<1,2,1,2>|up1,down2,k1', 'conv_f32_small_kernel<1,2,1,2>|up1,down2,k1'),
+    ((2, 96, 64, 8, 6, 1, 1, 1, 0), 'conv_f32_small_kernel<1,1,2,1>|up1,down1,k1', 'conv_f32_small_kernel<1,1,2,1>|up1,down1,k1', 'conv_f32_small_kernel<1,1,2,1>|up1,down1,k1'),
+    ((2, 64, 64, 4, 4, 3, 2, 1, 2), 'conv_f32_small_kernel<3,1,2,1>|up2,down1,k3', 'conv_f32_small_kernel<3,1,2,1>|up2,down1,k3', 'conv_f32_small_kernel<3,1,2,1>|up2,down1,k3'),
+    ((3, 128, 96, 17, 17, 3, 1, 2, 0), 'conv_f32_small_kernel<3,1,2,2>|up1,down2,k3', 'conv_f32_small_kernel<3,1,2,2>|up1,down2,k3', 'conv_f32_small_kernel<3,1,2,2>|up1,down2,k3'),
+    # conv_bf16x3_kernel<1,4,2,2> (64 oc x 8-row tiles) in its three geometries; the 32-oc and 4-row forms it leaves to the plain-bf16 lists
+    ((8, 16, 72, 128, 33, 3, 1, 1, 1), 'conv_bf16x3_kernel<1,4,2,2>|up1,down1,k3', 'conv_bf16x3_kernel<1,4,2,2>|up1,down1,k3', 'conv_mfma_kernel<2,2,1,8,2,2,32>|up1,down1,k3'),
+    ((8, 16, 72, 128, 33, 1, 1, 1, 0), 'conv_bf16x3_kernel<1,4,2,2>|up1,down1,k1', 'conv_bf16x3_kernel<1,4,2,2>|up1,down1,k1', 'conv_mfma_kernel<2,2,1,8,2,2,32>|up1,down1,k1'),
+    ((8, 16, 512, 9, 9, 3, 2, 1, 1), 'conv_bf16x3_kernel<1,4,2,2>|up2,down1,k3', 'conv_bf16x3_kernel<1,4,2,2>|up2,down1,k3', 'conv_mfma_kernel<1,1,4,32,1,1,16>|up2,down1,k3'),
+    ((1, 16, 3, 4, 9, 3, 2, 1, 1), 'conv_bf16x3_kernel<1,4,1,2>|up2,down1,k3', 'conv_bf16x3_kernel<1,4,1,2>|up2,down1,k3', 'conv_mfma_kernel<1,1,4,32,1,1,16>|up2,down1,k3'),
+    ((1, 16, 40, 4, 9, 1, 1, 1, 0), 'conv_bf16x3_kernel<1,4,2,1>|up1,down1,k1', 'conv_bf16x3_kernel<1,4,2,1>|up1,down1,k1', 'conv_mfma_kernel<1,1,4,32,1,1,16>|up1,down1,k1'),
+    ((2, 16, 24, 31, 31, 1, 1, 2, 0), 'conv_bf16x3_kernel<1,4,1,1>|up1,down2,k1', 'conv_bf16x3_kernel<1,4,1,1>|up1,down2,k1', 'conv_mfma_kernel<1,1,4,32,1,1,16>|up1,down2,k1'),
+    ((2, 40, 20, 71, 67, 3, 1, 2, 0), 'conv_bf16x3_kernel<1,4,1,1>|up1,down2,k3', 'conv_bf16x3_kernel<1,4,1,1>|up1,down2,k3', 'conv_mfma_kernel<2,2,1,8,1,1,32>|up1,down2,k3'),
+    ((1, 40, 64, 63, 63, 1, 1, 2, 0), 'conv_bf16x3_kernel<1,4,2,1>|up1,down2,k1', 'conv_bf16x3_kernel<1,4,2,1>|up1,down2,k1', 'conv_mfma_kernel<2,2,1,8,1,1,32>|up1,down2,k1'),
+    ((1, 16, 40, 9, 13, 3, 2, 1, 1), 'conv_bf16x3_kernel<1,4,2,1>|up2,down1,k3', 'conv_bf16x3_kernel<1,4,2,1>|up2,down1,k3', 'conv_mfma_kernel<1,1,4,32,1,1,16>|up2,down1,k3'),
+    # conv_bf16x3_ws_kernel<taps, oc blocks, column blocks>: 32-oc blocks (N = 96) on 32- and 64-px tiles, 64-oc blocks on 32-, 64- and 128-px tiles; heights that end
+    # one row into a 16-row tile, widths one pixel past a tile
+    ((4, 32, 96, 128, 33, 3, 1, 1, 1), 'conv_bf16x3_ws_kernel<3,1,1>|up1,down1,k3', 'conv_bf16x3_ws_kernel<3,1,1>|up1,down1,k3', 'conv_mfma_kernel<2,2,1,8,1,1,32>|up1,down1,k3'),
+    ((8, 32, 96, 33, 65, 3, 1, 1, 1), 'conv_bf16x3_ws_kernel<3,1,2>|up1,down1,k3', 'conv_bf16x3_ws_kernel<3,1,2>|up1,down1,k3', 'conv_mfma_kernel<2,2,1,8,1,1,32>|up1,down1,k3'),
+    ((4, 32, 96, 128, 33, 1, 1, 1, 0), 'conv_bf16x3_ws_kernel<1,1,1>|up1,down1,k1', 'conv_bf16x3_ws_kernel<1,1,1>|up1,down1,k1', 'conv_mfma_kernel<2,2,1,8,1,1,32>|up1,down1,k1'),
+    ((8, 32, 96, 33, 65, 1, 1, 1, 0), 'conv_bf16x3_ws_kernel<1,1,2>|up1,down1,k1', 'conv_bf16x3_ws_kernel<1,1,2>|up1,down1,k1', 'conv_mfma_kernel<2,2,1,8,1,1,32>|up1,down1,k1'),
+    ((4, 64, 512, 17, 65, 1, 1, 1, 0), 'conv_bf16x3_ws_kernel<1,2,2>|up1,down1,k1', 'conv_bf16x3_ws_kernel<1,2,2>|up1,down1,k1', 'conv_mfma_kernel<2,2,1,8,1,1,32>|up1,down1,k1'),
+    ((4, 48, 32, 150, 170, 1, 1, 1, 0), 'conv_bf16x3_ws_kernel<1,1,4>|up1,down1,k1', 'conv_bf16x3_ws_kernel<1,1,4>|up1,down1,k1', 'conv_mfma_kernel<1,4,1,8,1,4,32>|up1,down1,k1'),
+    ((8, 64, 384, 17, 33, 3, 1, 1, 1), 'conv_bf16x3_ws_kernel<3,2,1>|up1,down1,k3', 'conv_bf16x3_ws_kernel<3,2,1>|up1,down1,k3', 'conv_mfma_kernel<2,2,1,8,1,1,32>|up1,down1,k3'),
+    ((8, 64, 256, 17, 65, 3, 1, 1, 1), 'conv_bf16x3_ws_kernel<3,2,2>|up1,down1,k3', 'conv_bf16x3_ws_kernel<3,2,2>|up1,down1,k3', 'conv_mfma_kernel<2,2,1,8,1,1,32>|up1,down1,k3'),
+    # the fused transposed kernel's 32-oc / 32-column form; the thin 1x1 vector-ALU kernels on ragged planes
+    ((2, 32, 32, 16, 17, 3, 2, 1, 2), 'convt_fused_bf16x3_kernel<1,4,2,32>|up2,down1,k3', 'convt_fused_bf16x3_kernel<1,4,2,32>|up2,down1,k3', 'conv_mfma_kernel<1,4,1,8,1,4,32>|up2,down1,k3'),
+    ((1, 3, 33, 515, 511, 1, 1, 1, 0), 'pw_widen_kernel|up1,down1,k1', 'pw_widen_kernel|up1,down1,k1', 'pw_widen_kernel|up1,down1,k1'),
+    ((2, 20, 2, 363, 365, 1, 1, 1, 0), 'pw_narrow_kernel|up1,down1,k1', 'pw_narrow_kernel|up1,down1,k1', 'pw_narrow_kernel|up1,down1,k1'),
+]
+_CONV_REFS = {}
+
+
+def _conv_operands(case):
+    """The operands of test_conv2d_bf16x3_kernel for a case, and its geometry."""
+    from gan_control_amd.models.op._backend import ConvGeom
+    b, K, N, h, w, k, up, down, pad = case
+    gen = torch.Generator().manual_seed(hash(case) & 0xFFFF)
+    x = torch.randn(b, K, h, w, generator=gen)
+    wt = torch.randn(k, k, K, N, generator=gen)
+    si = torch.randn(b, K, generator=gen)
+    so = torch.rand(b, N, generator=gen) + 0.5
+    geom = ConvGeom(k, k, up, down, pad, pad, _out_size(h, k, up, down, pad, up > 1), _out_size(w, k, up, down, pad, up > 1))
+    return x, wt, si, so, geom
+
+
+def _conv_ref(case, what, x, wt, si, so, geom):
+    """EmulatedBackend.conv2d in fp64 -- 'plain': no scales, 'scaled': with si / so, 'rounded': no scales on x and w rounded to bf16 (round to nearest even:
+    what the plain-bf16 kernels multiply -- the staging's v_cvt_pk_bf16_f32, pack_weights_kernel's (__bf16) conversion).  Computed once per case and shared
+    by the three modes; only the latest case is kept."""
+    if case not in _CONV_REFS:
+        _CONV_REFS.clear()
+        _CONV_REFS[case] = {}
+    refs = _CONV_REFS[case]
+    if what not in refs:
+        emu = EmulatedBackend()
+        if what == 'rounded':
+            x, wt = x.bfloat16(), wt.bfloat16()
+        scales = (si.double(), so.double()) if what == 'scaled' else (None, None)
+        refs[what] = emu.conv2d(x.double(), wt.double(), *scales, geom)
+    return refs[what]
+
+
+@pytest.mark.parametrize('mode', ['bf16x3', 'bf16', 'f32'])
+@pytest.mark.parametrize('case,fast,single,exact', CONV_VARIANT_CASES, ids=['%d-%dto%d-%dx%d-k%du%dd%dp%d' % c[0] for c in CONV_VARIANT_CASES])
+def test_conv2d_variants(case, fast, single, exact, mode):
+    """Every forward kernel the convolution dispatch can pick that the lists above do not reach, against EmulatedBackend.conv2d in fp64 on a shape the dispatch
+    probe confirms to reach it, without scales and with si / so.  Bounds by the family reached (_conv_tol): 5e-6 exact fp32, 5e-5 split-bf16, 2e-2 plain bf16.
+    Plain bf16 also against fp64 on bf16-rounded operands (the scale-free call), within 5e-5: bf16 x bf16 products are exact in fp32, so only the fp32
+    accumulation is left, which the split-bf16 bound already covers over the same reductions.  One repeat launch is bit-identical."""
+    from gan_control_amd.utils.profiling import conv_variant
+    hip, _ = _be()
+    b, K, N, h, w = case[:5]
+    x, wt, si, so, geom = _conv_operands(case)
+    want = {'bf16x3': fast, 'bf16': single, 'f32': exact}[mode]
+    name = conv_variant(geom, N, b, K, mode, (h, w))
+    print('conv variant:', mode, case, name)
+    assert name.startswith(want), 'this shape is meant to reach ' + want
+    tol = _conv_tol(name, mode)
+    prev, hip.conv_mode = hip.conv_mode, mode
+    try:
+        xd, wd, sid, sod = x.to(DEV), wt.to(DEV), si.to(DEV), so.to(DEV)
+        for what, scales in (('plain', (None, None)), ('scaled', (sid, sod))):
+            out = hip.conv2d(xd, wd, *scales, geom)
+            err = rel_err(out, _conv_ref(case, what, x, wt, si, so, geom))
+            print('  %-7s rel_err %.3g (bound %g)' % (what, err, tol))
+            assert err < tol, (name, what, err)
+            if mode == 'bf16' and what == 'plain' and name.startswith(_BF16_FAMILIES):
+                err = rel_err(out, _conv_ref(case, 'rounded', x, wt, si, so, geom))
+                print('  rounded rel_err %.3g (bound 5e-05)' % err)
+                assert err < 5e-5, (name, 'bf16-rounded operands', err)
+            assert torch.equal(out, hip.conv2d(xd, wd, *scales, geom)), 'the convolution must be run-to-run deterministic'
+    finally:
+        hip.conv_mode = prev
+
+
 EPILOGUE_CASES = [c for c in BF16_CASES if c[1] >= 3 and c not in WS_CASES + SMALL_CASES + CT_SPLIT_CASES + CT_EDGE_CASES + S2WS_CASES][::2] + WS_CASES + SMALL_CASES[1:4] + SMALL_UP_CASES[:2] + SMALL_GROUP_CASES[:3] + CT_SPLIT_CASES[:3] + CT_EDGE_CASES[:3] + S2WS_CASES[:4]
+# ... and with them every forward variant of tests/golden/dispatch_table.json in each of the three modes (tests/test_dispatch.py::test_every_frozen_variant_has_a_kernel_case):
+# shapes of CONV_VARIANT_CASES and BF16_CASES for what the list above leaves out
+EPILOGUE_CASES = EPILOGUE_CASES + [
+    (8, 3, 72, 128, 33, 3, 1, 1, 1), (8, 3, 72, 128, 33, 1, 1, 1, 0), (8, 3, 72, 256, 80, 3, 1, 2, 0), (8, 3, 72, 256, 65, 1, 1, 2, 0),
+    (2, 3, 72, 128, 32, 3, 2, 1, 2), (2, 3, 72, 128, 33, 1, 2, 1, 0), (1, 3, 3, 4, 4, 1, 1, 1, 0), (1, 3, 3, 4, 4, 1, 1, 2, 0), (1, 3, 3, 4, 4, 1, 2, 1, 0),
+    (1, 3, 3, 4, 4, 3, 2, 1, 1), (1, 3, 3, 7, 7, 1, 1, 1, 0), (1, 3, 3, 6, 7, 3, 1, 1, 0), (1, 3, 3, 13, 13, 1, 1, 2, 0), (1, 3, 3, 15, 13, 3, 1, 2, 0),
+    (1, 3, 3, 7, 7, 1, 2, 1, 0), (1, 3, 3, 9, 13, 1, 1, 1, 0), (1, 3, 3, 9, 13, 3, 1, 1, 1), (1, 3, 3, 17, 27, 1, 1, 2, 0), (1, 3, 3, 17, 27, 3, 1, 2, 0),
+    (1, 3, 3, 9, 13, 1, 2, 1, 0), (1, 3, 3, 8, 13, 3, 2, 1, 2), (1, 3, 40, 17, 19, 3, 1, 1, 1), (1, 3, 40, 5, 17, 1, 2, 1, 0), (1, 3, 40, 16, 19, 3, 2, 1, 2),
+    (1, 3, 72, 17, 19, 1, 1, 1, 0), (1, 3, 72, 17, 19, 3, 1, 1, 1), (1, 3, 3, 9, 33, 1, 1, 2, 0), (1, 3, 3, 63, 65, 3, 1, 2, 0), (1, 3, 72, 5, 17, 1, 2, 1, 0),
+    (1, 64, 64, 4, 4, 1, 1, 1, 0), (1, 64, 64, 4, 4, 1, 1, 2, 0), (2, 96, 64, 8, 6, 1, 1, 1, 0), (3, 128, 96, 17, 17, 3, 1, 2, 0),
+    (8, 16, 72, 128, 33, 3, 1, 1, 1), (8, 16, 72, 128, 33, 1, 1, 1, 0), (8, 16, 512, 9, 9, 3, 2, 1, 1), (1, 16, 3, 4, 9, 3, 2, 1, 1),
+    (1, 16, 40, 4, 9, 1, 1, 1, 0), (2, 16, 24, 31, 31, 1, 1, 2, 0), (1, 16, 40, 9, 13, 3, 2, 1, 1), (4, 32, 96, 128, 33, 3, 1, 1, 1),
+    (8, 32, 96, 33, 65, 3, 1, 1, 1), (4, 32, 96, 128, 33, 1, 1, 1, 0), (8, 32, 96, 33, 65, 1, 1, 1, 0), (4, 64, 512, 17, 65, 1, 1, 1, 0),
+    (3, 128, 64, 9, 9, 1, 1, 2, 0), (1, 32, 32, 70, 40, 3, 1, 1, 1),
+]
+_EPILOGUE_REFS = {}
 
 
-@pytest.mark.parametrize('mode', ['f32', 'bf16x3'])
+@pytest.mark.parametrize('mode', ['f32', 'bf16x3', 'bf16'])
 @pytest.mark.parametrize('case', EPILOGUE_CASES)
 def test_conv2d_fused_epilogue(case, mode):
-    """gc_conv2d_fused_*: (noise +) bias + leaky-ReLU in the convolution epilogue == convolution followed by gc_bias_act_f32, bit for bit."""
+    """gc_conv2d_fused_*: (noise +) bias + leaky-ReLU in the convolution epilogue == convolution followed by gc_bias_act_f32, bit for bit; the fused output
+    against fp64 within 5e-6 (fp32) / 5e-5 (split-bf16) and, in plain bf16 (gc_conv2d_fused_bf16_packed_f32), within the bound of the family reached (_conv_tol).
+    The fp64 reference is shared by the three modes."""
     from gan_control_amd.models.op._backend import ConvGeom
+    from gan_control_amd.utils.profiling import conv_variant
     hip, emu = _be()
     prev, hip.conv_mode = hip.conv_mode, mode
     try:
@@ -617,10 +786,16 @@ def test_conv2d_fused_epilogue(case, mode):
             fused = hip.conv2d(x, wt, *scales, geom, epilogue=(bias, nz, nw, 0.2, 2 ** 0.5, True, res))
             assert torch.equal(fused, hip.bias_act(plain, bias, nz, nw, 0.2, 2 ** 0.5) + res)
         # against the independent emulation in fp64
-        ref = emu.conv2d(x.cpu().double(), wt.cpu().double(), si.cpu().double(), so.cpu().double(), geom,
-                         epilogue=(bias.cpu().double(), nz.cpu().double(), nw.cpu().double(), 0.2, 2 ** 0.5, True))
+        if case not in _EPILOGUE_REFS:
+            _EPILOGUE_REFS.clear()          # only the latest case is kept
+            _EPILOGUE_REFS[case] = emu.conv2d(x.cpu().double(), wt.cpu().double(), si.cpu().double(), so.cpu().double(), geom,
+                                              epilogue=(bias.cpu().double(), nz.cpu().double(), nw.cpu().double(), 0.2, 2 ** 0.5, True))
         out = hip.conv2d(x, wt, si, so, geom, epilogue=(bias, nz, nw, 0.2, 2 ** 0.5, True))
-        assert rel_err(out, ref) < (5e-6 if mode == 'f32' else 5e-5)
+        name = conv_variant(geom, N, b, K, mode, (h, w))
+        tol = _conv_tol(name, mode) if mode == 'bf16' else (5e-6 if mode == 'f32' else 5e-5)
+        err = rel_err(out, _EPILOGUE_REFS[case])
+        print('fused epilogue:', mode, case, name, 'rel_err %.3g (bound %g)' % (err, tol))
+        assert err < tol, (name, err)
     finally:
         hip.conv_mode = prev
 
@@ -1316,6 +1491,11 @@ SAMPLE_WGRAD_CASES = [
     (3, 512, 512, 32, 96, 3, 1, 1, False, 'wgrad_bf16x3_ws2_kernel|down1,k3|samples|plan:splits=9,tiles_per_split=16,bands=2'),  # wave-specialised: three splits per sample, two strips each
     (2, 64, 64, 65, 65, 3, 2, 0, False, 'wgrad_bf16x3_s2_kernel<1,3,2>|down2,k3|samples'),        # stride 2, 64k x 64n, one output row per tile
     (2, 64, 128, 64, 64, 1, 2, 0, False, 'wgrad_bf16x3_s2_kernel<1,1,1,4>|down2,k1|samples'),     # stride-2 1 x 1 (D's skip convolutions), 32k x 128n
+    (3, 70, 40, 13, 37, 1, 1, 0, False, 'wgrad_bf16x3_kernel<1,1,4,6,1>|down1,k1|samples'),       # 1 x 1 on 32 x 32 tiles of six rows, ragged channel tiles on both sides
+    (3, 64, 64, 34, 70, 1, 2, 0, False, 'wgrad_bf16x3_s2_kernel<1,1,2>|down2,k1|samples'),        # stride-2 1 x 1, 64k x 64n
+    (3, 32, 128, 34, 70, 1, 2, 0, False, 'wgrad_bf16x3_s2_kernel<2,1,1>|down2,k1|samples'),       # stride-2 1 x 1, 32k x 64n tiles of two rows
+    (2, 4, 64, 95, 97, 1, 1, 0, False, 'pw_wgrad_kernel<false>|thin_x|down1,k1|samples'),         # thin 1 x 1 on planes that are no multiple of four pixels
+    (2, 40, 3, 95, 97, 1, 1, 0, False, 'pw_wgrad_kernel<false>|thin_dy|down1,k1|samples'),
 ]
 
 

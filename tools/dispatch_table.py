@@ -10,6 +10,8 @@ columns, the histogram of kernel names -- and tests/test_dispatch.py recomputes 
     diff before.txt after.txt
 
     python tools/dispatch_table.py --write                      # regenerate tests/golden/dispatch_table.json (a deliberate change of a decision)
+
+    python tools/dispatch_table.py --cheapest                   # per probe column and kernel variant: the grid descriptor with the fewest MACs that reaches it
 """
 import argparse
 import collections
@@ -164,14 +166,47 @@ def digest():
     return out
 
 
+def macs(t):
+    """Multiply-adds of the convolution a descriptor tuple describes: batch * K * N * out pixels * taps."""
+    b, K, N, _, _, oh, ow, kh, kw = t[:9]
+    return b * K * N * oh * ow * kh * kw
+
+
+def cheapest():
+    """(column, variant) -> (MACs, descriptor tuple) of the grid's cheapest descriptor that reaches the variant (split plan stripped, rc* cells skipped);
+    the probe columns only.  How the kernel-level test cases find a shape for a variant."""
+    lib = _lib.load()
+    probes = [(name, fn, tt) for name, (fn, tt) in columns(lib).items() if '_variant[' in name]
+    best = {}
+    for t in grid():
+        d = _lib.ConvDesc(*t)
+        cost = macs(t)
+        for name, fn, transposed_too in probes:
+            if t[9] != 1 and not transposed_too:
+                continue
+            cell = fn(d).split('|plan:')[0]
+            if cell.startswith('rc'):
+                continue
+            key = (name, cell)
+            if key not in best or cost < best[key][0]:
+                best[key] = (cost, t)
+    return best
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('--dump', action='store_true', help='print every row (diff two builds when a digest moves)')
     ap.add_argument('--write', action='store_true', help='write the digest to tests/golden/dispatch_table.json')
+    ap.add_argument('--cheapest', action='store_true',
+                    help='per probe column and kernel variant, the cheapest grid descriptor reaching it: b,K,N,in_h,in_w,out_h,out_w,kh,kw,up,down,pad_y,pad_x,in_pitch,out_pitch')
     args = ap.parse_args()
     if args.dump:
         for group, row in rows():
             print(group + ' | ' + row)
+        return
+    if args.cheapest:
+        for (name, cell), (cost, t) in sorted(cheapest().items()):
+            print('%s | %s | %.3g MAC | %s' % (name, cell, cost, ','.join(map(str, t))))
         return
     text = json.dumps(digest(), indent=1) + '\n'
     if args.write:
