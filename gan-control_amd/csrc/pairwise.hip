@@ -22,11 +22,14 @@
 #include <cstdint>
 
 #include "common.h"
+#include "pairwise_tile.h"          // fetch / stage: the transposed LDS staging, shared with manifold.hip
 
 namespace {
 
-constexpr int KC = 32;                 // columns per LDS chunk
-constexpr int NT = 256;                // threads per workgroup of the tile kernel
+using gc_tile::KC;
+using gc_tile::NT;
+using gc_tile::fetch;
+using gc_tile::stage;
 constexpr int MIN_SPLIT_CHUNKS = 8;    // a K split is at least 8 chunks (256 columns) long
 constexpr int TARGET_GROUPS = 1024;    // workgroups wanted per launch (4 per CU)
 constexpr int BIG_TILE_GROUPS = 256;   // R = 2 only where 128 x 128 tiles x possible splits reach one workgroup per CU
@@ -54,41 +57,6 @@ Plan plan_of(int m, int n, int k) {
     p.per = gc::ceil_div(p.chunks, p.splits);
     p.splits = gc::ceil_div(p.chunks, p.per);
     return p;
-}
-
-// This thread's share of a T x KC operand chunk: 2 R words of 4 columns (8 words per row, consecutive lanes along the row).
-template <int R, bool VEC>
-__device__ __forceinline__ void fetch(float4 (&reg)[2 * R], const float* __restrict__ base, long long stride, int rows, int row0, int k, int k0,
-                                      int tid) {
-#pragma unroll
-    for (int u = 0; u < 2 * R; ++u) {
-        const int f = tid + u * NT;
-        const int row = row0 + (f >> 3), col = k0 + (f & 7) * 4;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (row < rows && col < k) {
-            const float* p = base + (long long)row * stride + col;
-            if (VEC) {          // k % 4 == 0: the word ends inside the row
-                v = *reinterpret_cast<const float4*>(p);
-            } else {
-                v.x = p[0];
-                if (col + 1 < k) v.y = p[1];
-                if (col + 2 < k) v.z = p[2];
-                if (col + 3 < k) v.w = p[3];
-            }
-        }
-        reg[u] = v;
-    }
-}
-
-template <int R>
-__device__ __forceinline__ void stage(const float4 (&reg)[2 * R], float* image, int tid) {
-    constexpr int LD = 64 * R + 4;
-#pragma unroll
-    for (int u = 0; u < 2 * R; ++u) {
-        const int f = tid + u * NT;
-        float* dst = image + (f & 7) * 4 * LD + (f >> 3);
-        dst[0] = reg[u].x; dst[LD] = reg[u].y; dst[2 * LD] = reg[u].z; dst[3 * LD] = reg[u].w;
-    }
 }
 
 // grid: (column tile, row tile, K split).  out: D (one split; div = K for ABS) or the workspace (split_stride = m * n; div = 1).

@@ -161,6 +161,12 @@ SIGNATURES = {
     'gc_group_moments_workspace': (_sz, [_i32, _vp, _vp, _i32]),
     'gc_group_moments_f32': (_i32, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
     'gc_group_project_f32': (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
+    'gc_knn_radius_workspace': (_sz, [_i32, _i32, _i32]),
+    'gc_knn_radius_f32': (_i32, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _sz, _vp]),
+    'gc_manifold_hits_workspace': (_sz, [_i32, _i32, _i32]),
+    'gc_manifold_hits_f32': (_i32, [_vp, _i64, _vp, _i32, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    'gc_poly_mmd_workspace': (_sz, [_i32, _i32, _i32]),
+    'gc_poly_mmd_f32': (_i32, [_vp, _i64, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

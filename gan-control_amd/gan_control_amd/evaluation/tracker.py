@@ -3,7 +3,9 @@ the FID history that decides when ``best_fid.pt`` is written, and the separabili
 
 The orientation / expression / age matrices and histograms (they need the external predictors), the matplotlib plots and tensorboard are
 out of scope; the FID history goes to ``<graph_save_path>/fid.json`` and the separability history to
-``<graph_save_path>/separability.json`` instead of plots.
+``<graph_save_path>/separability.json`` instead of plots.  Beyond the reference: with ``fid_config['kid']`` / ``fid_config['precision_recall']``
+the FID sample also yields KID and improved precision / recall (fid_utils/kid.py, fid_utils/precision_recall.py), kept in
+``<graph_save_path>/quality.json``; without those keys nothing changes.
 
 Separability (tracker.py:134-155, :185-311) runs for the losses that are BOTH listed in ``separability_config['losses']`` and present in the
 ``loss_models`` handed to ``evaluate``.  Two deliberate deviations from the reference's ``evaluate``: it indexes ``training_config`` for five
@@ -65,13 +67,29 @@ class Tracker:
                                          debug=debug, same_chunks=same_chunks)
 
     def fid_evaluation(self, iter, model, graph_save_path=None, debug=False):
+        """FID of a fresh sample; with ``fid_config['kid']`` / ``fid_config['precision_recall']`` also KID / precision and recall of the SAME
+        sample (fid.evaluate_quality), into ``evaluation_dict`` and ``<graph_save_path>/quality.json``."""
         cfg = self.fid_config
-        fid = float(fid_module.evaluate_fid(model, self.inception, 20, 100 if debug else cfg['num_of_samples'], self._device(model),
-                                            cfg.get('inception_stat_path')))
+        n_sample = 100 if debug else cfg['num_of_samples']
+        extra = [m for m in ('kid', 'precision_recall') if cfg.get(m)]
+        quality = None
+        if extra:
+            quality = fid_module.evaluate_quality(model, self.inception, 20, n_sample, self._device(model), cfg.get('inception_stat_path'),
+                                                  metrics=['fid'] + extra)
+            quality = {k: float(v) for k, v in quality.items()}
+            fid = quality['fid']
+        else:
+            fid = float(fid_module.evaluate_fid(model, self.inception, 20, n_sample, self._device(model), cfg.get('inception_stat_path')))
         self.fids.append(fid)
         self.evaluation_dict['fid'] = fid
         if graph_save_path is not None:
             self._append_history(os.path.join(graph_save_path, 'fid.json'), {'iter': int(iter), 'fid': fid})
+        if quality is not None:
+            for key in ('kid', 'precision', 'recall'):
+                if key in quality:
+                    self.evaluation_dict[key] = quality[key]
+            if graph_save_path is not None:
+                self._append_history(os.path.join(graph_save_path, 'quality.json'), dict({'iter': int(iter)}, **quality))
         return fid
 
     @staticmethod

@@ -19,8 +19,8 @@ def _batch_plan(n_sample, batch_size):
 
 
 @torch.no_grad()
-def sample_features(generator, feature_net, batch_size, n_sample, device='cuda', training=True, latent_dim=512, generator_fn=None):
-    """Features of ``n_sample`` generated images, on the host, in generation order.
+def sample_features(generator, feature_net, batch_size, n_sample, device='cuda', training=True, latent_dim=512, generator_fn=None, to_host=True):
+    """Features of ``n_sample`` generated images, in generation order: on the host, or with ``to_host=False`` on the device that made them.
 
     ``feature_net(img)[0]`` is flattened per image (fid.py:34); single-channel images are replicated to three channels
     (fid.py:32-33).  ``training`` only silences the progress output in the reference and is accepted for call compatibility.
@@ -32,7 +32,8 @@ def sample_features(generator, feature_net, batch_size, n_sample, device='cuda',
         if img.shape[1] == 1:
             img = img.expand(-1, 3, -1, -1)
         f = feature_net(img)[0]
-        feats.append(f.reshape(img.shape[0], -1).to('cpu'))
+        f = f.reshape(img.shape[0], -1)
+        feats.append(f.to('cpu') if to_host else f)
     return torch.cat(feats, 0)
 
 
@@ -75,3 +76,48 @@ def evaluate_fid(generator, feature_net, batch, n_sample, device, inception_stat
     fid = frechet_distance(mean, cov, real['mean'], real['cov'])
     print('fid: %.3f, time: %.3f (min)' % (fid, (time.time() - t0) / 60))
     return fid
+
+
+QUALITY_METRICS = ('fid', 'kid', 'precision_recall')
+
+
+def evaluate_quality(generator, feature_net, batch, n_sample, device, inception_stat_path, metrics=QUALITY_METRICS, training=False, kth=3,
+                     num_subsets=100, max_subset_size=1000, seed=0):
+    """The chosen ``metrics`` of ONE sample of ``n_sample`` generated images -> a dict with 'fid', 'kid', 'precision' and 'recall' (those asked for).
+
+    FID is ``evaluate_fid``'s host formula on a host copy of the generated features (the same value for the same RNG state; unlike
+    ``evaluate_fid`` the pickle is read and checked BEFORE anything is sampled).  When a metric beside FID is asked for, the features stay
+    whole on the device -- n_sample x F floats more at the peak than ``evaluate_fid``, which moves them batch by batch; with
+    ``metrics=('fid',)`` they are moved batch by batch here too.  KID (kid.py) and precision / recall (precision_recall.py) compare them on the device with the real features, the
+    float32 ``'features'`` array that ``real_stats.save_real_features`` pickles beside {'mean', 'cov'}."""
+    from .kid import kid
+    from .precision_recall import precision_recall
+    unknown = [m for m in metrics if m not in QUALITY_METRICS]
+    if unknown or not metrics:
+        raise ValueError('evaluate_quality: metrics must be some of %s, got %r' % (QUALITY_METRICS, tuple(metrics)))
+    t0 = time.time()
+    generator.eval()
+    if hasattr(feature_net, 'eval'):
+        feature_net.eval()
+    with open(inception_stat_path, 'rb') as f:
+        real = pickle.load(f)
+    need_features = [m for m in metrics if m != 'fid']
+    if need_features and real.get('features') is None:
+        raise ValueError("evaluate_quality: %s has no 'features' and %s need the real features themselves: write it with "
+                         "fid_utils.real_stats.save_real_features" % (inception_stat_path, ' and '.join(need_features)))
+    feats = sample_features(generator, feature_net, batch, n_sample, device, training=training, to_host=not need_features)
+    print(f'extracted {feats.shape[0]} features')
+    out = {}
+    if 'fid' in metrics:
+        mean, cov = feature_statistics(feats.to('cpu').numpy())
+        out['fid'] = frechet_distance(mean, cov, real['mean'], real['cov'])
+    if need_features:
+        feats = feats.float()
+        real_feats = torch.from_numpy(np.ascontiguousarray(real['features'], dtype=np.float32)).to(feats.device)
+        with torch.no_grad():
+            if 'kid' in metrics:
+                out['kid'] = kid(real_feats, feats, num_subsets=num_subsets, max_subset_size=max_subset_size, seed=seed)
+            if 'precision_recall' in metrics:
+                out.update(precision_recall(real_feats, feats, kth=kth))
+    print(', '.join('%s: %.4g' % kv for kv in out.items()) + ', time: %.3f (min)' % ((time.time() - t0) / 60))
+    return out

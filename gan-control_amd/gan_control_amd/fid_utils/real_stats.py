@@ -1,4 +1,5 @@
-"""Inception statistics of a folder of REAL images: the {'mean', 'cov'} pickle ``fid.evaluate_fid`` compares generated images against.
+"""Inception statistics of a folder of REAL images: the {'mean', 'cov'} pickle ``fid.evaluate_fid`` compares generated images against, and
+with ``save_real_features`` the features themselves for the metrics that need them (``fid.evaluate_quality``: KID, precision / recall).
 
 Reference: fid_utils/calc_inception.py:61-80 (``extract_features``: every batch of the loader through ``inception(img)[0]``, flattened per
 image, collected on the host) and its ``__main__`` (mean and ``np.cov`` of the features, pickled).  The batches come from a
@@ -31,4 +32,15 @@ def save_real_statistics(path, features):
     mean, cov = feature_statistics(f)
     with open(path, 'wb') as fh:
         pickle.dump({'mean': mean, 'cov': cov}, fh)
+    return mean, cov
+
+
+def save_real_features(path, features):
+    """``save_real_statistics``'s pickle plus ``'features'``: the float32 [n, F] matrix itself, which KID and precision / recall compare
+    generated features against (``fid.evaluate_quality``).  ``evaluate_fid`` reads the same file."""
+    host = features.detach().cpu() if torch.is_tensor(features) else torch.as_tensor(features)
+    f = host.double().numpy()
+    mean, cov = feature_statistics(f)
+    with open(path, 'wb') as fh:
+        pickle.dump({'mean': mean, 'cov': cov, 'features': host.float().numpy()}, fh)
     return mean, cov

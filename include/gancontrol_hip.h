@@ -889,6 +889,48 @@ int gc_group_moments_f32(const float* w, int64_t stride, int n, const int32_t* l
 int gc_group_project_f32(float* x, int64_t stride, int rows, const float* mean, const float* const* components, const int32_t* ranks,
                          const int32_t* lo, const int32_t* hi, int groups, gc_stream_t stream);
 
+/* ---- distance passes of the sample-quality metrics (models/op/manifold.py, csrc/manifold.hip) ---------------------------------------------
+ * Improved precision / recall (Kynkaanniemi et al. 2019) and KID (Binkowski et al. 2018) on DEVICE float32 feature rows: row i of a set at
+ * p + i * stride (strides in ELEMENTS, at least k; elements of a row adjacent; any 4-byte alignment: features[::2] is read in place).
+ * Squared distances are D[i, j] = sum_c (a[i, c] - b[j, c])^2 in float32 fused multiply-adds over c ascending: the difference itself, as
+ * GC_PAIRWISE_SQ, never |a|^2 + |b|^2 - 2 a.b.  The loop nest and the LDS staging are those of gc_pairwise_f32 (16-byte loads when every
+ * base is 16-byte aligned and every stride and k are multiples of 4, else 4-byte loads; no byte past a row's k-th element is loaded), but no
+ * m x n value is stored: a workgroup walks a strip of tiles and keeps what the tile epilogue reduces to, and a second launch merges the
+ * strips' partial results from the workspace in ascending strip order.  At most GC_MANIFOLD_STRIPS strips a side whatever the extents, so
+ * every workspace is O((m + n) * GC_MANIFOLD_STRIPS); the queries are functions of the extents alone (0 for extents outside the limits).
+ * At most two launches per call, no atomics, no workgroup waits for another, every sum and merge in an order fixed by the extents: the same
+ * inputs give the same bits.  Every element of the outputs is stored by the call; the caller zeroes nothing.  Inputs are assumed finite.
+ * Each entry refuses null pointers, extents below 1 and strides below k with GC_ERR_BAD_ARG, a short workspace with GC_ERR_WORKSPACE and more
+ * than 65535 * 64 rows a side with GC_ERR_UNSUPPORTED; nothing is launched and no output is touched then.
+ *
+ * gc_knn_radius_f32: radius2[i] (float[n]) = the (kth + 1)-th smallest value of row i of D(a, a), the row's own 0 included: the squared
+ * distance to the kth nearest OTHER row (torch's kthvalue(kth + 1)).  1 <= kth <= GC_KNN_MAX_KTH and n >= kth + 1, else GC_ERR_BAD_ARG.
+ * The tile epilogue keeps each row's kth + 1 smallest values of the columns of its strip, ascending; the finish pass merges the lists.
+ *
+ * gc_manifold_hits_f32: one pass over D(ref [m, k], probe [n, k]):
+ *   probe_hit[j] (uint8[n]) = any_i D[i, j] <= ref_radius2[i]            (probe j lies in the ref manifold)
+ *   ref_hit[i]   (uint8[m]) = any_j D[i, j] <= probe_radius2[j]          (with probe_radius2 and ref_hit: both given or both null)
+ * The comparison is <=: a tie is a hit.  With ref = real and probe = fake features, mean(probe_hit) is precision and mean(ref_hit) recall.
+ * One of the pair without the other returns GC_ERR_BAD_ARG.
+ *
+ * gc_poly_mmd_f32: for each subset s < subsets, with X_i = x[idx_x[s, i]] and Y_i = y[idx_y[s, i]], i < m (idx_*: DEVICE int32 [subsets, m];
+ * the rows are gathered inside the kernel; values outside [0, nx) / [0, ny) are the caller's error) and kappa(u, v) = (u.v / k + 1)^3:
+ *   sums[s, 0] = sum_{i != j} kappa(X_i, X_j)      sums[s, 1] = sum_{i != j} kappa(Y_i, Y_j)      sums[s, 2] = sum_{i, j} kappa(X_i, Y_j)
+ * (DEVICE double [subsets, 3]).  u.v in float32 fused multiply-adds over c ascending; the division, the cube and every partial and final
+ * sum in float64.  subsets <= 21845, else GC_ERR_UNSUPPORTED. */
+#define GC_MANIFOLD_STRIPS 32
+#define GC_KNN_MAX_KTH 7
+size_t gc_knn_radius_workspace(int n, int k, int kth);
+int gc_knn_radius_f32(const float* a, int64_t a_stride, int n, int k, int kth, float* radius2, void* workspace, size_t workspace_bytes,
+                      gc_stream_t stream);
+size_t gc_manifold_hits_workspace(int m, int n, int k);
+int gc_manifold_hits_f32(const float* ref, int64_t ref_stride, const float* ref_radius2, int m, const float* probe, int64_t probe_stride,
+                         const float* probe_radius2, int n, int k, uint8_t* probe_hit, uint8_t* ref_hit, void* workspace,
+                         size_t workspace_bytes, gc_stream_t stream);
+size_t gc_poly_mmd_workspace(int subsets, int m, int k);
+int gc_poly_mmd_f32(const float* x, int64_t x_stride, int nx, const float* y, int64_t y_stride, int ny, int k, const int32_t* idx_x,
+                    const int32_t* idx_y, int subsets, int m, double* sums, void* workspace, size_t workspace_bytes, gc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
