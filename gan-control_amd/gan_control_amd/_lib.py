@@ -152,6 +152,9 @@ SIGNATURES = {
     'gc_fc_train_launches': (_i64, []),
     'gc_pairwise_workspace': (_sz, [_i32, _i32, _i32]),
     'gc_pairwise_f32': (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'gc_pair_hinge_workspace': (_sz, [_i32, _i32]),
+    'gc_pair_hinge_fwd_f32': (_i32, [_vp, _i64, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'gc_pair_hinge_bwd_f32': (_i32, [_vp, _i64, _i32, _vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp]),
     'gc_latent_interp_f32': (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp]),
     'gc_noise_blend_f32': (_i32, [_vp, _vp, _vp, _vp, _i32, _f32, _f32, _vp]),
     'gc_weight_layout_f32': (_i32, [_vp, _vp, _i32, _i32, _i32, ctypes.POINTER(_i64 * 3), ctypes.POINTER(_i64 * 3), _i32, _f32, _vp]),

@@ -19,7 +19,13 @@ The evaluation half of the class (loss_model.py:204-321) is here as well: ``calc
 ``calc_same_not_same_list``, ``L1Expend`` and ``get_same_not_same_list``, which the separability evaluation (evaluation/separability.py) runs
 on thousands of samples.  Their all-pairs distances and per-query minima are ``models.op.pairwise.pairwise_distances`` -- one HIP call on
 device features under that module's dispatch rule, the reference's chunked formula otherwise.  ``calc_mini_batch_loss`` does not use it: the
-mini-batch losses keep their autograd torch formulas.
+mini-batch losses keep their autograd torch formulas by default.
+
+``LossModelClass(..., fused=True)`` sends every level whose criterion is one of ``CRITERIA`` (or ``L1Expend``'s formula) through
+``models.op.pair_hinge.pair_hinge_loss``: one HIP call forward and one backward per level under that module's dispatch rule, the same torch
+expression otherwise.  The hair criterion's masked colour means stay torch ops under autograd (two reductions of a ``[n, 4, 256, 256]``
+tensor); only the hinge on the resulting ``[n, 3]`` colours, with the rows' validity flags, is the fused call.  ``calc_mini_batch_loss_rows``
+is the index form: the whole mini-batch's features plus the rows in "same block, then the rest" order, so nothing is sliced or concatenated.
 """
 import torch
 
@@ -42,6 +48,51 @@ CRITERIA = {
 }
 
 
+def _hair_colours(features):
+    """[n, 4, h, w] (masked image, mask) -> ([n, 3] mean hair colour in [0, 1], [n, 1] bool: more than 1 % of the pixels are hair)
+    (hair_criterion.py:17-36).  The mask sum carries no gradient; an empty mask divides by one."""
+    h, w = features.shape[-2:]
+    mask_sum = torch.sum(features[:, 3:, :, :].detach(), dim=[-2, -1])
+    colours = torch.div(torch.sum(features[:, :3, :, :], dim=[-2, -1]), mask_sum + (mask_sum < 0.5).float())
+    return colours.mul(0.5).add(0.5), mask_sum > 0.01 * w * h
+
+
+def _hair_distance(signatures, queries):
+    """hair_criterion.py:16-44: mean absolute colour difference, zero where either row has (almost) no hair.  The mini-batch loss hands
+    the same tensor in twice: its colours are reduced once (one node in the autograd graph, as on the fused path)."""
+    s, s_valid = _hair_colours(signatures)
+    q, q_valid = (s, s_valid) if queries is signatures else _hair_colours(queries)
+    diff = (s.unsqueeze(1) - q.unsqueeze(0)) * (s_valid.unsqueeze(1) * q_valid.unsqueeze(0))
+    return diff.abs().mean(-1)
+
+
+def _hair_predict(features):
+    """hair_criterion.py:46-54: the colour, zeroed where the mask is empty."""
+    mask_sum = torch.sum(features[:, 3:, :, :].detach(), dim=[-2, -1])
+    preds = torch.div(torch.sum(features[:, :3, :, :], dim=[-2, -1]), mask_sum + (mask_sum < 0.5).float())
+    return preds.mul(0.5).add(0.5) * (mask_sum > 0.5)
+
+
+RECON_LOSS_NAMES = ('recon_3d_loss', 'recon_id_loss', 'recon_ex_loss', 'recon_tex_loss', 'recon_angles_loss', 'recon_gamma_loss', 'recon_xy_loss',
+                    'recon_z_loss')
+# the 3DMM coefficient vector [n, 257] and the sub-loss that reads each slice (face3dmm_skeleton.py:36-38)
+RECON_SLICES = (('id', 0, 80), ('ex', 80, 144), ('tex', 144, 224), ('angles', 224, 227), ('gamma', 227, 254), ('xy', 254, 256), ('z', 256, 257))
+
+CRITERIA['hair_loss'] = _hair_distance
+# style_criterion.py:11-16 (mean squared difference of [c, c] Gram matrices, times 1e5)
+STYLE_SCALE = 1e5
+CRITERIA['style_loss'] = _pairwise(lambda d: d.pow(2).mean((-2, -1)) * STYLE_SCALE)
+# face3dmm_criterion.py:14-21 (mean absolute difference over the last axis), one function for the predictor and its seven slices
+CRITERIA.update(dict.fromkeys(RECON_LOSS_NAMES, _pairwise(lambda d: d.abs().mean(-1))))
+
+
+def extract_futures_from_vec(features):
+    """The last feature [n, 257] of the 3DMM predictor cut into (id, ex, tex, angles, gamma, xy, z), each a one-element feature list
+    (face3dmm_skeleton.py:36-38).  Views, never copies: the fused losses read the slices in place."""
+    vec = features[-1]
+    return tuple([vec[:, lo:hi]] for _, lo, hi in RECON_SLICES)
+
+
 def _expected_bin(logits):
     """softmax expectation over the class index: DEX age head (deep_age_criterion.py:24-33)."""
     prob = torch.softmax(logits, dim=-1)
@@ -58,7 +109,11 @@ PREDICTORS = {
     'age_loss': (_expected_bin, lambda pred, target: torch.nn.functional.mse_loss(pred, target)),
     # hopenet_criterion.py:6-19, 38-43: three 66-bin heads -> degrees; L1 against the controls
     'orientation_loss': (lambda f: _expected_bin(f) * 3 - 99, lambda pred, target: (pred - target).abs().mean()),
+    # hair_criterion.py:46-57
+    'hair_loss': (_hair_predict, lambda pred, target: torch.nn.functional.mse_loss(pred, target)),
 }
+# face3dmm_criterion.py:23-24: no predict() in the reference (the controller reads the slice itself)
+PREDICTORS.update(dict.fromkeys(RECON_LOSS_NAMES, (None, lambda pred, target: torch.abs(pred - target).mean())))
 
 
 def _l1_expand(features):
@@ -71,8 +126,9 @@ class LossModelClass:
     last_lower_thres / last_upper_thres / last_layer_weight, focus_on_list (one entry per level incl. the last)."""
 
     def __init__(self, config, loss_name='embedding_loss', mini_batch_size=4, device='cuda', no_model=False, parallel=True,
-                 skeleton_model=None, criterion=None, predict_fn=None, controller_criterion_fn=None):
+                 skeleton_model=None, criterion=None, predict_fn=None, controller_criterion_fn=None, fused=False):
         self.config, self.loss_name = config, loss_name
+        self.fused = bool(fused)          # calc_mini_batch_loss through models.op.pair_hinge (module docstring); never with a custom criterion
         if skeleton_model is None and not no_model:
             raise RuntimeError('LossModelClass(%s): the pretrained predictor is not part of this repository; pass skeleton_model=<frozen '
                                'network returning the list of features>, or no_model=True to use the loss on precomputed features' % loss_name)
@@ -137,6 +193,11 @@ class LossModelClass:
         if last_layer_not_same_features is None:
             raise ValueError('last_layer_not_same_features is None')
         same, other = last_layer_same_features, last_layer_not_same_features
+        if self.fused:
+            levels = len(same)
+            wanted = [level == levels - 1 or self.weights[level] != 0 for level in range(levels)]
+            return self.calc_mini_batch_loss_rows([torch.cat([same[level], other[level]], dim=0) if wanted[level] else None for level in range(levels)],
+                                                  None, same[0].shape[0], other[0].shape[0])
         masks = self.pair_masks(same[0].shape[0], other[0].shape[0], device=same[-1].device)
         as_last = bool(self.config.get('intermediate_criterion_as_last_layer'))
         loss = 0
@@ -149,6 +210,38 @@ class LossModelClass:
         emb = torch.cat([same[-1], other[-1]], dim=0)
         dist = self.last_layer_criterion(emb, emb)
         return loss + self.weights[-1] * self._level_loss(dist, masks, self.focus_on_list[-1], self.last_lower_thres, self.last_upper_thres)
+
+    def calc_mini_batch_loss_rows(self, features_list, rows, n_same, n_not_same):
+        """calc_mini_batch_loss on the WHOLE mini-batch's features: ``rows`` lists the rows in "same block, then the rest" order
+        (MiniBatchUtils.same_not_same_rows; None: the rows as they are), the first ``n_same`` of them the same block.  With ``fused`` every
+        level whose criterion has a kernel form is one pair_hinge_loss call that reads the rows in place; any other level -- and every level
+        without ``fused`` -- picks the rows with one index and runs the criterion and _level_loss as calc_mini_batch_loss does."""
+        if features_list is None:
+            raise ValueError('features_list is None')
+        from ..models.op import pair_hinge
+        as_last = bool(self.config.get('intermediate_criterion_as_last_layer'))
+        levels = len(features_list)
+        loss = 0
+        for level in range(levels):
+            last = level == levels - 1
+            if not last and self.weights[level] == 0:
+                continue
+            feats = features_list[level]
+            fn = self.last_layer_criterion if (last or as_last) else None          # None: L1Expend's formula (_l1_expand)
+            lower, upper = (self.last_lower_thres, self.last_upper_thres) if last else (self.lower_thres[level], self.upper_thres[level])
+            weight, focus = self.weights[-1 if last else level], self.focus_on_list[-1 if last else level]
+            form = _hinge_form(fn, feats) if self.fused else None
+            if form is None:
+                picked = feats if rows is None else feats[list(rows)]
+                dist = fn(picked, picked) if fn is not None else _l1_expand(picked)
+                level_loss = weight * self._level_loss(dist, self.pair_masks(n_same, n_not_same, device=feats.device), focus, lower, upper)
+            elif form[0] == 'hair':
+                colours, valid = _hair_colours(feats)
+                level_loss = pair_hinge.pair_hinge_loss(colours, n_same, n_not_same, 'abs', lower, upper, focus, weight, rows, valid)
+            else:
+                level_loss = pair_hinge.pair_hinge_loss(feats, n_same, n_not_same, form[0], lower, upper, focus, weight, rows, None, form[1])
+            loss = loss + level_loss
+        return loss
 
     # -- the evaluation half (loss_model.py:204-285): all-pairs distances of two feature sets and their same / not-same split ----------
     def calc_distances_list(self, signatures_list, queries_list, last_layer_separability_only=False):
@@ -240,6 +333,24 @@ class L1Expend(torch.nn.Module):
 # itself is called, and what it returns is checked (the squared-L2 criterion leaves [m, n, c, h] on 4-D maps)
 _KERNEL_FORMS = [(CRITERIA['embedding_loss'], 'sq', (2,)), (CRITERIA['dog_id_loss'], 'sq', (2,)), (CRITERIA['orientation_loss'], 'abs', (3,)),
                  (CRITERIA['expression_loss'], 'abs', (3,)), (CRITERIA['age_loss'], 'abs', (2,))]
+
+
+def _hinge_form(criterion, features):
+    """(mode of models.op.pair_hinge, scale) of a mini-batch level under ``criterion`` (None: L1Expend's formula), or None where the criterion
+    has no kernel form on these rows (a custom callable, a rank the criterion does not reduce to a matrix): the torch path.  ('hair', 1.0):
+    the hair criterion, whose colours are computed first."""
+    if criterion is None:
+        return ('abs', 1.0) if features.dim() == 4 else None
+    if criterion is CRITERIA['hair_loss']:
+        return ('hair', 1.0) if features.dim() == 4 else None
+    if criterion is CRITERIA['style_loss']:
+        return ('msq', STYLE_SCALE) if features.dim() == 3 else None
+    if criterion is CRITERIA['recon_3d_loss']:
+        return ('abs', 1.0) if features.dim() == 2 else None
+    for fn, mode, ranks in _KERNEL_FORMS:
+        if criterion is fn:
+            return (mode, 1.0) if features.dim() in ranks else None
+    return None
 
 
 def _mode_of(distance_fn, signatures):

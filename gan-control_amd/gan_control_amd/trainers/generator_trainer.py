@@ -135,13 +135,33 @@ class GeneratorTrainer:
         if self.local_mini_batch >= 4 and self.local_mini_batch % 4 != 0:
             raise ValueError('per-GPU mini-batch must be a multiple of 4 (minibatch-stddev groups, gan_model.py:1005-1011)')
         self.batch_utils = None
+        self.random_places = self.fused_attribute_losses = False
+        self.recon_sub_losses = {}
         if self.loss_models and not self.model_config.get('vanilla', True):
             # the same / not-same pairs are positions inside ONE mini-batch (mini_batch_multi_split_utils.py:64-69): every rank must
             # run whole mini-batches (last row)
             if self.local_mini_batch != tc['mini_batch']:
                 raise ValueError('attribute losses need whole mini-batches per rank: batch / world must be a multiple of mini_batch')
-            from ..utils.mini_batch_utils import MiniBatchUtils
-            self.batch_utils = MiniBatchUtils(tc['mini_batch'], tc['sub_groups_dict'], total_batch=tc['batch'], latent_size=self.model_config['latent_size'])
+            from ..utils.mini_batch_utils import MiniBatchUtils, RandomMiniBatchUtils
+            self.random_places = tc.get('mini_batch_mode') == 'random'          # generator_trainer.py:48-53
+            utils_class = RandomMiniBatchUtils if self.random_places else MiniBatchUtils
+            self.batch_utils = utils_class(tc['mini_batch'], tc['sub_groups_dict'], total_batch=tc['batch'], latent_size=self.model_config['latent_size'])
+            # training_config.fused_attribute_losses: the hinge stage of every loss through models.op.pair_hinge on the whole mini-batch's
+            # features and a row index (profiles/attribute_losses.md); absent / false: the torch formulas on slices, as before
+            self.fused_attribute_losses = bool(tc.get('fused_attribute_losses', False))
+            if self.fused_attribute_losses:
+                for model in self.loss_models.values():
+                    model.fused = True
+            # recon_3d_loss: ONE predictor whose [n, 257] vector feeds up to seven sub-losses, each with its own thresholds and group
+            # (generator_trainer.py:240-255): the enabled ones, built once
+            self.recon_sub_losses = {}
+            if 'recon_3d_loss' in self.loss_models:
+                from ..losses.loss_model import LossModelClass, RECON_SLICES
+                for x, _, _ in RECON_SLICES:
+                    sub_cfg = tc['recon_3d_loss'].get(x + '_loss')
+                    if sub_cfg and sub_cfg.get('enabled'):
+                        self.recon_sub_losses[x] = LossModelClass(sub_cfg, 'recon_%s_loss' % x, mini_batch_size=tc['mini_batch'], no_model=True,
+                                                                  fused=self.fused_attribute_losses)
         self.gen = torch.Generator(device=self.device)
         self.gen.manual_seed(seed * 1000 + self.rank)
         torch.manual_seed(seed)          # identical initial weights on every rank
@@ -340,10 +360,16 @@ class GeneratorTrainer:
         zero_grad_none(self.generator)
         n = len(mini_noise_inputs)
         for name in (self.loss_models if self.batch_utils is not None else ()):
+            if name == 'recon_3d_loss':          # its sub-losses report under the reference's keys (generator_trainer.py:480-516)
+                for x in self.recon_sub_losses:
+                    self.stats[x + '_loss'] = 0
+                continue
             self.stats['g_' + name] = 0
         for k, z in enumerate(mini_noise_inputs):
             self.g_reducer.begin(sync=(k == n - 1), phase='g')
             if self.batch_utils is not None:
+                if self.random_places:
+                    self.batch_utils.randomize_places_in_batch()                        # generator_trainer.py:413-414
                 z = self.batch_utils.re_arrange_z([t.clone() for t in z], k)           # generator_trainer.py:412-415
             fake_img, _ = self.generator(z, noise=noise)
             if self.training_config['augment']['enabled']:                       # generator_trainer.py:421-424
@@ -362,18 +388,34 @@ class GeneratorTrainer:
 
     def attribute_losses(self, fake_img, n_mini_batches):
         """Sum over the enabled predictor losses of weight * (pull the same-attribute pairs together + push the rest apart)
-        (calc_id_losses / calc_pose_losses, generator_trainer.py:438-547: the same three lines per loss)."""
+        (calc_id_losses / calc_pose_losses, generator_trainer.py:438-547: the same three lines per loss).  recon_3d_loss is one calc_features
+        call whose last feature is cut into the slices of the enabled sub-losses (generator_trainer.py:473-517)."""
         total = 0
         for name, model in self.loss_models.items():
             cfg = self.training_config[name]
             if not cfg.get('enabled', True):
                 continue
             feats = model.calc_features(fake_img)
-            same, other = self.batch_utils.extract_same_not_same_from_list(feats, cfg['same_group_name'])
-            loss = model.calc_mini_batch_loss(last_layer_same_features=same, last_layer_not_same_features=other) / n_mini_batches
+            if name == 'recon_3d_loss':
+                from ..losses.loss_model import RECON_SLICES, extract_futures_from_vec
+                for (x, _, _), futures in zip(RECON_SLICES, extract_futures_from_vec(feats)):
+                    if x in self.recon_sub_losses:
+                        group = cfg[x + '_loss']['same_group_name']
+                        loss = self._mini_batch_loss(self.recon_sub_losses[x], futures, group) / n_mini_batches
+                        self.stats[x + '_loss'] = self.stats[x + '_loss'] + loss.detach()
+                        total = total + loss
+                continue
+            loss = self._mini_batch_loss(model, feats, cfg['same_group_name']) / n_mini_batches
             self.stats['g_' + name] = self.stats['g_' + name] + loss.detach()
             total = total + loss
         return total
+
+    def _mini_batch_loss(self, model, feats, group):
+        if self.fused_attribute_losses:
+            rows, n_same, n_not_same = self.batch_utils.same_not_same_rows(group)
+            return model.calc_mini_batch_loss_rows(feats, rows, n_same, n_not_same)
+        same, other = self.batch_utils.extract_same_not_same_from_list(feats, group)
+        return model.calc_mini_batch_loss(last_layer_same_features=same, last_layer_not_same_features=other)
 
     def generator_regularize_step(self, noise=None, pl_noise=None, z=None):
         tc = self.training_config

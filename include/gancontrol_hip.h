@@ -819,6 +819,43 @@ int gc_pairwise_f32(const float* s, int64_t s_stride, const float* q, int64_t q_
                     const int32_t* s_pid, const int32_t* q_pid, float* best, int32_t* best_idx, void* workspace, size_t workspace_bytes,
                     gc_stream_t stream);
 
+/* ---- the same / not-same hinge loss of one feature level of the attribute stage (models/op/pair_hinge.py, csrc/pair_hinge.hip) ------------
+ * What LossModelClass.calc_mini_batch_loss computes per level (loss_model.py:121-181) and its gradient, without the cat / mask gathers.
+ * f: n_rows rows of k values, row r at f + r * stride (stride in ELEMENTS, at least k; elements of a row adjacent; any 4-byte alignment: a
+ * column slice vec[:, 227:254] is read in place).  row_index: HOST int32 [n] or null -- the rows of f in pair order ("same block, then the
+ * rest"), distinct and inside [0, n_rows); it is checked and copied into the kernel arguments by the call (null: n_rows == n, in order).
+ * row_valid: DEVICE float [n_rows] or null -- v_r = 1 where the entry is non-zero, else 0 (null: all 1); GC_PAIR_HINGE_ABS only reads it.
+ * With n = n_same + n_not_same, for the pairs i > j of the pair order:
+ *   GC_PAIR_HINGE_ABS: D[i, j] = v_i v_j (sum_c |F_i,c - F_j,c|) / k      (the mean-absolute criteria, L1Expend, the hair criterion)
+ *   GC_PAIR_HINGE_SQ:  D[i, j] = sum_c (F_i,c - F_j,c)^2                    (squared L2)
+ *   GC_PAIR_HINGE_MSQ: D[i, j] = (sum_c (F_i,c - F_j,c)^2) / k * scale      (the style criterion, scale = 1e5)
+ * The pair sets are those of LossModelClass.pair_masks + _level_loss: 'same' = the pairs (j + 1, j), j even, with j < 2 (n_same / 2)
+ * (GC_PAIR_HINGE_FOCUS_SAME) or 2 (n_same / 2) <= j < 2 (n_same / 2) + 2 (n_not_same / 2) (GC_PAIR_HINGE_FOCUS_NOT_SAME); 'rest' = every
+ * other pair below the diagonal.  Forward writes loss[0] = weight * (mean over same of max(D - lower, 0) + mean over rest of max(upper - D, 0)),
+ * d [n, n] = D and c [n, n] = dloss / dD (weight / count where the hinge is active -- at zero too, as torch.clamp -- else 0); both are zero
+ * on and above the diagonal.  n k <= GC_PAIR_HINGE_ONE_LAUNCH_VALUES: one launch of one workgroup; longer rows: a tile launch split along k
+ * that writes partial sums to the workspace and a one-workgroup launch that adds them in a fixed order and finishes.
+ * Backward, one launch: df [n_rows, k] DENSE, df[row_index[i], c] = g[0] * sum_{j != i} C[max(i, j), min(i, j)] v_i v_j phi'(F_i,c - F_j,c) with
+ * phi'(x) = sign(x) / k (ABS; sign(0) = 0), 2 x (SQ), 2 scale x / k (MSQ); rows of f outside row_index get zeros.  g: DEVICE float [1].
+ * No atomics; every sum in an order fixed by (n, k): the same inputs give the same bits.  Workspace: gc_pair_hinge_workspace(n, k) bytes (0
+ * for one-launch shapes and for refused extents).  Null pointers, k < 1, n < 2, n_rows < n (or != n without an index), a stride below k, an
+ * unknown mode or focus, a bad or repeated row_index entry and an empty pair set return GC_ERR_BAD_ARG, n > GC_PAIR_HINGE_MAX_ROWS or
+ * n_rows > GC_PAIR_HINGE_MAX_BATCH_ROWS GC_ERR_UNSUPPORTED, a short workspace GC_ERR_WORKSPACE.  Nothing is launched then. */
+#define GC_PAIR_HINGE_ABS 0
+#define GC_PAIR_HINGE_SQ 1
+#define GC_PAIR_HINGE_MSQ 2
+#define GC_PAIR_HINGE_FOCUS_SAME 0
+#define GC_PAIR_HINGE_FOCUS_NOT_SAME 1
+#define GC_PAIR_HINGE_MAX_ROWS 64
+#define GC_PAIR_HINGE_MAX_BATCH_ROWS 1024
+#define GC_PAIR_HINGE_ONE_LAUNCH_VALUES 8192
+size_t gc_pair_hinge_workspace(int n, int k);
+int gc_pair_hinge_fwd_f32(const float* f, int64_t stride, int n_rows, const int32_t* row_index, const float* row_valid, int n_same, int n_not_same,
+                          int k, int mode, float scale, int focus, float lower, float upper, float weight, float* loss, float* d, float* c,
+                          void* workspace, size_t workspace_bytes, gc_stream_t stream);
+int gc_pair_hinge_bwd_f32(const float* f, int64_t stride, int n_rows, const int32_t* row_index, const float* row_valid, int n, int k, int mode,
+                          float scale, const float* c, const float* g, float* df, gc_stream_t stream);
+
 /* ---- group interpolation of the inference API (models/op/interp.py, csrc/interp.hip) --------------------------------------------------------
  * The blends of Inference.interpolate_by_group (reference: evaluation/inference_class.py:125-185), each in one launch.
  *
