@@ -172,6 +172,13 @@ SIGNATURES = {
     'gc_poly_mmd_f32': (_i32, [_vp, _i64, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _sz, _vp]),
 }
 
+# the entries of include/gancontrol_stats.h (streaming feature statistics, csrc/feature_stats.hip): a table of its own, bound after SIGNATURES
+STATS_SIGNATURES = {
+    'gc_feature_moments_accumulate_f32': (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _vp]),
+    'gc_feature_moments_finish_f64': (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),
+    'gc_feature_moments_merge_f64': (_i32, [_vp, _vp, _vp, _vp, _i32, _vp]),
+}
+
 _lib = None
 
 
@@ -202,7 +209,7 @@ def load():
         lib = ctypes.CDLL(path)
     except OSError as e:
         raise RuntimeError(f'gan_control_amd: cannot load {path}: {e}') from e
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(STATS_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

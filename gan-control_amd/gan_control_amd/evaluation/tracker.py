@@ -5,7 +5,9 @@ The orientation / expression / age matrices and histograms (they need the extern
 out of scope; the FID history goes to ``<graph_save_path>/fid.json`` and the separability history to
 ``<graph_save_path>/separability.json`` instead of plots.  Beyond the reference: with ``fid_config['kid']`` / ``fid_config['precision_recall']``
 the FID sample also yields KID and improved precision / recall (fid_utils/kid.py, fid_utils/precision_recall.py), kept in
-``<graph_save_path>/quality.json``; without those keys nothing changes.
+``<graph_save_path>/quality.json``; without those keys nothing changes.  ``fid_config['streaming']`` and ``fid_config['fid_method']`` are
+handed to ``evaluate_fid`` / ``evaluate_quality`` as ``streaming=`` and ``method=`` (device-resident statistics, eigen-form distance);
+without these keys the calls are the ones made before.
 
 Separability (tracker.py:134-155, :185-311) runs for the losses that are BOTH listed in ``separability_config['losses']`` and present in the
 ``loss_models`` handed to ``evaluate``.  Two deliberate deviations from the reference's ``evaluate``: it indexes ``training_config`` for five
@@ -72,14 +74,16 @@ class Tracker:
         cfg = self.fid_config
         n_sample = 100 if debug else cfg['num_of_samples']
         extra = [m for m in ('kid', 'precision_recall') if cfg.get(m)]
+        # fid_config['streaming'] / ['fid_method'] -> the keywords of the same names; without the keys the calls are made without them
+        opts = {kw: cfg[key] for key, kw in (('streaming', 'streaming'), ('fid_method', 'method')) if key in cfg}
         quality = None
         if extra:
             quality = fid_module.evaluate_quality(model, self.inception, 20, n_sample, self._device(model), cfg.get('inception_stat_path'),
-                                                  metrics=['fid'] + extra)
+                                                  metrics=['fid'] + extra, **opts)
             quality = {k: float(v) for k, v in quality.items()}
             fid = quality['fid']
         else:
-            fid = float(fid_module.evaluate_fid(model, self.inception, 20, n_sample, self._device(model), cfg.get('inception_stat_path')))
+            fid = float(fid_module.evaluate_fid(model, self.inception, 20, n_sample, self._device(model), cfg.get('inception_stat_path'), **opts))
         self.fids.append(fid)
         self.evaluation_dict['fid'] = fid
         if graph_save_path is not None:

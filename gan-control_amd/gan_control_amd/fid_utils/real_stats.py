@@ -9,6 +9,7 @@ import pickle
 
 import torch
 
+from .feature_stats import FeatureStats
 from .fid import feature_statistics
 
 
@@ -26,10 +27,34 @@ def extract_real_features(stream, feature_net, n_images):
     return torch.cat(feats, 0)[:n_images]
 
 
+@torch.no_grad()
+def stream_real_statistics(stream, feature_net, n_images):
+    """``extract_real_features`` without the features: every batch of ``stream`` goes into a ``FeatureStats`` on the device that made it (the
+    last batch trimmed to ``n_images``); nothing is kept and nothing copied to the host.  -> the ``FeatureStats``."""
+    if getattr(stream, 'training', False):
+        raise ValueError('real statistics are taken without flip or crop: build the stream with training=False')
+    stats, have = None, 0
+    while have < n_images:
+        img, _ = next(stream)
+        f = feature_net(img)[0]
+        f = f.reshape(img.shape[0], -1)[:n_images - have]
+        if stats is None:
+            stats = FeatureStats(f.shape[1], f.device)
+        stats.append(f)
+        have += f.shape[0]
+    if stats is None:
+        raise ValueError('stream_real_statistics: no images asked for (n_images = %r)' % (n_images,))
+    return stats
+
+
 def save_real_statistics(path, features):
-    """Pickle {'mean', 'cov'} of a [n, F] feature matrix where ``evaluate_fid(..., inception_stat_path=path)`` reads it."""
-    f = features.double().numpy() if torch.is_tensor(features) else features
-    mean, cov = feature_statistics(f)
+    """Pickle {'mean', 'cov'} of a [n, F] feature matrix -- or of a ``FeatureStats`` (``stream_real_statistics``) -- where
+    ``evaluate_fid(..., inception_stat_path=path)`` reads it."""
+    if isinstance(features, FeatureStats):
+        mean, cov = features.numpy()
+    else:
+        f = features.double().numpy() if torch.is_tensor(features) else features
+        mean, cov = feature_statistics(f)
     with open(path, 'wb') as fh:
         pickle.dump({'mean': mean, 'cov': cov}, fh)
     return mean, cov
